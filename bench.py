@@ -16,6 +16,16 @@ N > 1: independent chains, one per GPU (weak scaling, no collective on the data 
 every --rhat-every steps the chains exchange Welford moments with one RCCL all-reduce
 to compute R-hat (the only communication the path has).
 
+A plain run (no ``--full``) does only what the line's headline needs: set-up, the untimed phases, the timed steps, the
+outputs if ``--dump-outputs DIR`` is given, the line. ``--full`` adds everything measured after the timed region (the legs
+below, the CPU baseline, the ESS estimate, ``value_product_defaults``, the collective alone for N > 1, the other stepping
+modes of ``sinc-bnn``).
+
+``--dump-outputs DIR``: after the timed steps, what the last one handed its caller -- for the BNN chains the sample (one
+``sample_<k>.npy`` per parameter tensor) and ``cost.npy`` -- as float32 (float64 for ``--dtype f64``) ``.npy`` files, at most
+64 MB in all (a fixed, seeded sample of positions of each output beyond that, ``benchlib/dump.py``). The inputs (data, initial
+weights, minibatch windows, noise) are seeded: the same arguments give the same inputs in every run.
+
 Phases: (1) PRIME, always and untimed, independent of --warmup: the chain's burn-in (8 adapting
 steps), then frozen steps with a Welford moments update, a trace append and (N > 1) one complete
 R-hat exchange -- every code path the timed loop can take has run once (first use of a kernel
@@ -26,12 +36,12 @@ Other workloads (``--workload``): ``bnn50m-sgld`` / ``bnn50m-rsghmc`` (configs[4
 (configs[1], the reference's own 3 x 50 BNN test case: fused whole-step kernel vs hipGraph vs eager), ``svgd16-10m``.
 The pieces live in ``benchlib/`` (launcher, workloads, the timed chain run, post-run legs, CPU baselines).
 
-Output: ONE JSON line on rank 0. ``value`` = whole-job samples/s over the whole timed region
-(``step_ms_median`` / ``step_ms_max`` from per-step HIP events expose one-offs). ``roofline`` = the
-fused update kernel measured live with HIP events inside the timed region (10 M parameters: 240 MB
-per launch, Infinity-Cache-assisted); ``roofline_hbm_resident`` = the same kernels on 49 826 818
+Output: ONE JSON line on rank 0. ``value`` = whole-job samples/s over the whole timed region, ``ms_per_step`` = the
+timed region's milliseconds per step (``step_ms_median`` / ``step_ms_max`` from per-step HIP events expose one-offs).
+``roofline`` = the fused update kernel measured live with HIP events inside the timed region (10 M parameters: 240 MB
+per launch, Infinity-Cache-assisted). With ``--full``: ``roofline_hbm_resident`` = the same kernels on 49 826 818
 parameters (1.2 GB per launch, cannot live in the 256 MiB Infinity Cache), measured after the
-timed region. ``cpu_baseline`` (N = 1 only) = the same full step on the host cores (numpy/BLAS
+timed region; ``cpu_baseline`` (N = 1 only) = the same full step on the host cores (numpy/BLAS
 BNN gradient + the fused C oracle update), unit samples/s like ``value``. N > 1 lines also carry ``value_ex_exchange``
 (samples/s with the exposed time of the R-hat exchange taken out of the timed region) and ``rccl.exposed_ms``.
 """
@@ -83,13 +93,18 @@ def parse():
                     help="arithmetic type of the chain: f64 is the reference's default dtype (pysgmcmc/samplers/base_classes.py:25); the f64 "
                          "line carries `value`, the step's device time and the update kernel's roofline (16 B per f64 element touch) -- "
                          "no legs after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement after the timed region (kernel-alone loops, step breakdown, HBM-resident sizes, "
+                         "CPU baseline, value_product_defaults, ESS, the collective alone, the other sinc-bnn modes); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--product-defaults", action="store_true",
                     help="step the same chain with NOTHING set (no pysgmcmc_amd.configure_for_device_bound_chains()): the rate a "
                          "user of the public API gets by default; the main line runs this as a child process (value_product_defaults)")
-    ap.add_argument("--no-product-defaults", action="store_true", help="skip the value_product_defaults child run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-update-only", action="store_true", help="skip the kernel-only loops (for rocprof runs)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the CPU baseline leg")
+    ap.add_argument("--no-product-defaults", action="store_true", help="skip the value_product_defaults child run (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (--full)")
+    ap.add_argument("--no-update-only", action="store_true", help="skip the kernel-only loops (--full; for rocprof runs)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the CPU baseline leg (--full)")
     return ap.parse_args()
 
 
@@ -152,10 +167,13 @@ def main():
     if args.product_defaults:                                  # the child leg of value_product_defaults: the rate only
         print(json.dumps({"value": line["value"], "ms_per_step": line["ms_per_step"], "config": line["config"]}))
         return
-    run.leave_group(line)                                      # N > 1: the collective alone, then the job ends for every rank
+    run.leave_group(line)                                      # N > 1: (--full: the collective alone,) then the job ends for every rank
     if rank != 0:
         return
-    if args.dtype == "f32":
+    if args.dump_outputs:                                      # before any leg steps the chain further
+        from benchlib.dump import dump_outputs
+        dump_outputs(args.dump_outputs, run.outputs())
+    if args.full and args.dtype == "f32":
         run.post_run_legs(line)                                # kernel alone, step breakdown, HBM-resident sizes, CPU baseline
     print(json.dumps(line))
     sys.stdout.flush()

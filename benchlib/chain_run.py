@@ -2,7 +2,8 @@
 ``next(sampler)``, with the fused Welford moments, the thinned ESS trace and -- for N > 1 -- the asynchronous R-hat exchange.
 
 Phases (``ChainBench.prime`` / ``warmup`` / ``timed``): see the module docstring of ``bench.py``. ``headline()`` builds the
-JSON line from what the timed region recorded; ``post_run_legs()`` adds the measurements taken after it."""
+JSON line from what the timed region recorded; ``outputs()`` hands out what the last timed step computed; with ``--full``,
+``post_run_legs()`` adds the measurements taken after it (the ESS estimate and the collective-alone timing are --full ones too)."""
 import gc
 import os
 import sys
@@ -81,9 +82,10 @@ class ChainBench(object):
         for chain, mom in zip(self.chains, self.all_moments):
             chain.attach_moments(mom if every else None, every or 1)
         if group is None:
-            _, cost = next(sampler)
+            self.last = [next(sampler)]                        # [(sample, cost)]: what a caller of next(sampler) receives
         else:
-            cost = next(group)[0][1]                           # every chain of this GPU, round-robin on their streams
+            self.last = next(group)                            # every chain of this GPU, round-robin on their streams
+        cost = self.last[0][1]
         if every and sampler.n_iterations % every == 0:        # this step's update folded theta' into the moments
             with torch.cuda.stream(group.streams[0] if group is not None else torch.cuda.current_stream(self.dev)):
                 self.trace[self.kept, 0:1].copy_(cost.reshape(1))      # (the thinned ESS trace follows the GPU's first chain)
@@ -213,7 +215,7 @@ class ChainBench(object):
         self.elapsed = elapsed
         assert torch.isfinite(self.sampler.arena.row("theta")).all()
         self.ess = None
-        if self.kept >= self.ESS_MIN_KEPT:
+        if self.kept >= self.ESS_MIN_KEPT and getattr(args, "full", False):
             from pysgmcmc_amd.diagnostics.sampler_diagnostics import ess_across_ranks
             self.ess = ess_across_ranks(self.trace[:self.kept].contiguous())     # all-gather of kept x 4 floats (untimed)
 
@@ -306,6 +308,8 @@ class ChainBench(object):
             self._rccl_fields(line)
         if self.ess is not None:
             line["ess"] = {"kept_per_chain": self.kept, "cost": self.ess[0], "theta_coords": self.ess[1:]}
+        elif self.kept >= self.ESS_MIN_KEPT:
+            line["ess"] = {"kept_per_chain": self.kept, "cost": None, "theta_coords": None, "note": "estimated with --full only"}
         else:
             # pymc3's effective_n formula is unguarded (diagnostics/sampler_diagnostics.py): on a handful of samples it returns
             # anything, negative numbers included -- not reported below ESS_MIN_KEPT kept samples per chain
@@ -354,11 +358,21 @@ class ChainBench(object):
         line["rhat"] = {k: round(v, 4) for k, v in ex.summary.as_dict().items()} if ex.exchanges else None
 
     # ------------------------------------------------------------------ after the timed region
+    def outputs(self):
+        """What the last timed step handed its caller, as (name, tensor) pairs: every chain's sample (the parameter tensors,
+        ``sample_<k>``; chains after the GPU's first one prefixed ``chain<c>_``) and its cost."""
+        out = []
+        for c, (sample, cost) in enumerate(self.last):
+            pre = "chain%d_" % c if c else ""
+            sample = sample if isinstance(sample, (list, tuple)) else [sample]
+            out += [("%ssample_%02d" % (pre, k), v) for k, v in enumerate(sample)] + [(pre + "cost", cost)]
+        return out
+
     def leave_group(self, line):
-        """All ranks: the collective alone (blocking, same payload), then the job ends for every rank -- rank 0's extra legs
-        run with no process group alive, so no rank sits in a collective (or its watchdog) while they take their seconds."""
+        """All ranks: with --full the collective alone (blocking, same payload), then the job ends for every rank -- rank 0's
+        extra legs run with no process group alive, so no rank sits in a collective (or its watchdog) while they take their seconds."""
         dist, ex = self.dist, self.exchange
-        if ex is not None:
+        if ex is not None and getattr(self.args, "full", False):
             torch.cuda.synchronize()
             dist.barrier()
             ts = []

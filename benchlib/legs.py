@@ -205,8 +205,9 @@ def gemm_only_us(sampler, iters=60):
     with torch.cuda.stream(side):
         flops = gemms()
     torch.cuda.current_stream().wait_stream(side)
+    from pysgmcmc_amd.samplers.base_classes import graph_capture
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+    with graph_capture(graph, capture_error_mode="thread_local"):
         gemms()
     for _ in range(5):
         graph.replay()

@@ -5,8 +5,8 @@ eps = 0.01, mdecay = 0.05, scale_grad = N = 100, burn_in_steps = 1000), 5 252 pa
 
 A step of this size is launch-bound, not bandwidth-bound (the whole state is 147 KB): ``value`` is the rate of the product's
 default path for it -- the fused whole-step kernel K8 (``sgmcmc_bnn_fused_sghmc_steps_f32``: window gather, net, NLL, gradients,
-update, burn-in switch, up to 100 steps per launch in ONE workgroup) -- and ``modes`` reports the same chain stepped through
-``next(sampler)`` eagerly, with the cost pipeline replayed from a hipGraph, and with the whole step in one graph."""
+update, burn-in switch, up to 100 steps per launch in ONE workgroup) -- and, with ``--full``, ``modes`` reports the same chain
+stepped through ``next(sampler)`` eagerly, with the cost pipeline replayed from a hipGraph, and with the whole step in one graph."""
 import json
 import sys
 import gc
@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from benchlib.common import HBM_PEAK_GBS, usable_cores
+from benchlib.dump import dump_outputs
 
 N_POINTS, BATCH_SINC, BURN_IN, CHUNK = 100, 20, 1000, 100
 
@@ -132,7 +133,7 @@ def run_sinc(args, dev, rank, world, dist):
     t0 = time.perf_counter()
     for k, (e0, e1) in zip(launches, pairs):
         e0.record()
-        s.fused_bnn_steps(k)
+        costs = s.fused_bnn_steps(k)
         e1.record()
     fence()
     elapsed = time.perf_counter() - t0
@@ -146,8 +147,34 @@ def run_sinc(args, dev, rank, world, dist):
     assert torch.isfinite(s.arena.row("theta")).all()
     if rank != 0:
         return
+    if args.dump_outputs:                                      # the chain's sample and the costs of the last timed launch
+        dump_outputs(args.dump_outputs, [("sample_%02d" % k, v) for k, v in enumerate(s.arena.views("theta"))] + [("costs", costs)])
     launch_us = np.array([a.elapsed_time(b) for a, b in pairs]) * 1e3
     us_per_step = float(launch_us.sum() / args.steps)
+    line = {
+        "metric": "MCMC samples/sec, sinc BNN 3x50 (BASELINE configs[1])",
+        "value": round(world * args.steps / elapsed, 1), "unit": "samples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "sinc-bnn: SGHMC (frozen phase) on the reference's BNN test case, tanh MLP 1-50-50-50-1 + "
+                               "log-variance = %d params, 100 points of sinc(10 x - 5), batch 20, eps 0.01, mdecay 0.05, "
+                               "scale_grad 100, burn-in 1000 (done in the prime phase); whole steps in the fused kernel, "
+                               "%d steps per launch; 1 chain per GPU" % (n, CHUNK),
+                   "params": n, "batch": BATCH_SINC, "chains": world, "steps_per_launch": CHUNK},
+        "roofline": sinc_roofline(n, us_per_step, launch_us, len(launches)),
+    }
+    if args.full:
+        line["modes_samples_per_s"], line["many_chains_per_gpu"] = sinc_legs(dev)
+        if world == 1 and not args.no_cpu_baseline:
+            line["cpu_baseline"] = sinc_cpu_baseline(min(args.cpu_seconds, 8.0))
+    print(json.dumps(line))
+    sys.stdout.flush()
+
+
+def sinc_legs(dev):
+    """--full: the other stepping modes of the same chain and the ensemble form of its kernel (after the timed region)."""
+    sync = torch.cuda.synchronize
     # the other stepping modes of the same chain (after the timed region, fresh chains, burn-in by the fused kernel first)
     modes = {"fused_steps_%d_per_launch" % CHUNK: None}
     fused = build_sinc_chain(dev, 0)
@@ -186,33 +213,19 @@ def run_sinc(args, dev, rank, world, dist):
             "note": "one launch advances %d independent chains by %d steps (one 512-lane workgroup per chain, one chain per CU); "
                     "samples_per_s is wall clock including the host side (window draws of every chain), not part of `value`" % (n_chains, CHUNK)}
         del group
+    return modes, many
+
+
+def sinc_roofline(n, us_per_step, launch_us, n_launches):
     alg_bytes = 6 * 4 * n + BATCH_SINC * 2 * 4                 # R{theta, V, grad, minv} W{theta, V} + the window rows, if it went to HBM
-    line = {
-        "metric": "MCMC samples/sec, sinc BNN 3x50 (BASELINE configs[1])",
-        "value": round(world * args.steps / elapsed, 1), "unit": "samples/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "sinc-bnn: SGHMC (frozen phase) on the reference's BNN test case, tanh MLP 1-50-50-50-1 + "
-                               "log-variance = %d params, 100 points of sinc(10 x - 5), batch 20, eps 0.01, mdecay 0.05, "
-                               "scale_grad 100, burn-in 1000 (done in the prime phase); whole steps in the fused kernel, "
-                               "%d steps per launch; 1 chain per GPU" % (n, CHUNK),
-                   "params": n, "batch": BATCH_SINC, "chains": world, "steps_per_launch": CHUNK},
-        "modes_samples_per_s": modes,
-        "many_chains_per_gpu": many,
-        "roofline": {"bound": "hbm", "kernel": "bnn_fused_sghmc_kernel<float, 0> (ONE 512-lane workgroup per chain)",
-                     "achieved": round(alg_bytes / (us_per_step * 1e-6) / 1e9, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(alg_bytes / (us_per_step * 1e-6) / 1e9 / HBM_PEAK_GBS, 6), "traffic": None,
-                     "algorithmic_bytes_per_step": alg_bytes, "us_per_step": round(us_per_step, 2),
-                     "us_per_launch_mean": round(float(launch_us.mean()), 1), "launches_timed": len(launches),
-                     "us_per_launch": [round(float(v), 1) for v in launch_us[:16]],
-                     "note": "latency-bound, one workgroup: the chain's whole state (%d KB) lives in LDS / L2 for the length of a "
-                             "launch, so the HBM roofline does not bind -- a step is ~25 barrier-separated phases of 8 waves "
-                             "on one CU (DESIGN.md section 3, K8); the figure that matters is us_per_step. rocprofv3 launch "
-                             "durations: profiles/r04_sinc_bnn_kernel_stats.csv" % (7 * 4 * n // 1024),
-                     "timing": "hipEvent pair around every launch of the timed region"},
-    }
-    if world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = sinc_cpu_baseline(min(args.cpu_seconds, 8.0))
-    print(json.dumps(line))
-    sys.stdout.flush()
+    return {"bound": "hbm", "kernel": "bnn_fused_sghmc_kernel<float, 0> (ONE 512-lane workgroup per chain)",
+            "achieved": round(alg_bytes / (us_per_step * 1e-6) / 1e9, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(alg_bytes / (us_per_step * 1e-6) / 1e9 / HBM_PEAK_GBS, 6), "traffic": None,
+            "algorithmic_bytes_per_step": alg_bytes, "us_per_step": round(us_per_step, 2),
+            "us_per_launch_mean": round(float(launch_us.mean()), 1), "launches_timed": n_launches,
+            "us_per_launch": [round(float(v), 1) for v in launch_us[:16]],
+            "note": "latency-bound, one workgroup: the chain's whole state (%d KB) lives in LDS / L2 for the length of a "
+                    "launch, so the HBM roofline does not bind -- a step is ~25 barrier-separated phases of 8 waves "
+                    "on one CU (DESIGN.md section 3, K8); the figure that matters is us_per_step. rocprofv3 launch "
+                    "durations: profiles/r04_sinc_bnn_kernel_stats.csv" % (7 * 4 * n // 1024),
+            "timing": "hipEvent pair around every launch of the timed region"}

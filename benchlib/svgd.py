@@ -8,6 +8,7 @@ import torch
 
 from benchlib.baselines import svgd_cpu_baseline
 from benchlib.common import HBM_PEAK_GBS
+from benchlib.dump import dump_outputs
 from benchlib.workloads import WORKLOADS
 
 
@@ -75,7 +76,9 @@ def run_svgd(args, dev, rank, world, dist):
                          "launches_timed": len(pairs),
                          "timing": "hipEvent pair around every step (4 launches) of the timed region"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:                                  # the particles and the AdaGrad history the step updates in place
+            dump_outputs(args.dump_outputs, [("particles", x.view(n, ld)[:, :dim]), ("hist_grad", hist.view(n, ld)[:, :dim])])
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = svgd_cpu_baseline(n, dim, args.cpu_seconds)
         print(json.dumps(line))
         sys.stdout.flush()

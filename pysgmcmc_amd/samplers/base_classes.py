@@ -33,6 +33,8 @@ What differs, by design:
     ``"device"`` (cloned device tensors) or ``"view"`` (zero-copy views of the
     live arena; they change at the next step).
 """
+import contextlib
+import gc
 import logging
 import os
 
@@ -52,6 +54,23 @@ _DTYPES = {
     np.dtype("float32"): torch.float32, np.dtype("float64"): torch.float64,
     float: torch.float64,
 }
+
+
+@contextlib.contextmanager
+def graph_capture(graph, **kwargs):
+    """``torch.cuda.graph(graph, **kwargs)`` with Python's cyclic garbage collector run BEFORE the capture and kept off until it
+    ends. A collection that fires inside a capture finalises whatever dead cycles it finds -- e.g. an earlier sampler holding
+    captured graphs, whose private memory pool is then released by the capturing thread, which the runtime refuses (the
+    process aborts). Memory released by plain reference counting during the capture is unaffected."""
+    gc.collect()
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kwargs):
+            yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 def as_torch_dtype(dtype):
@@ -629,7 +648,7 @@ class MCMCSampler(object):
         graph = torch.cuda.CUDAGraph()
         # thread_local: other threads (e.g. the RCCL watchdog of a multi-chain job) may keep calling
         # HIP while this thread captures
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        with graph_capture(graph, capture_error_mode="thread_local"):
             cost = self._cost_and_grad()
         return graph, cost
 
@@ -638,7 +657,7 @@ class MCMCSampler(object):
         graph = torch.cuda.CUDAGraph()
         self._capturing = True
         try:
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            with graph_capture(graph, capture_error_mode="thread_local"):
                 cost = self._cost_and_grad()
                 with torch.no_grad():
                     self._update(eps, None)

@@ -25,7 +25,7 @@ def test_sinc_bnn_workload_is_configs_1(gpu):
     """BASELINE configs[1] (SGHMC on the reference's 3 x 50 sinc BNN, its own test case
     ``tests/bayesian_neural_network/test_train_predict.py:20-48``) as a bench line: the fused whole-step kernel's rate as
     `value`, the hipGraph / eager rates of the same chain next to it, the same step on a host core as `cpu_baseline`."""
-    d = _bench(["--workload", "sinc-bnn", "--steps", "400", "--warmup", "50", "--cpu-seconds", "3"])
+    d = _bench(["--workload", "sinc-bnn", "--steps", "400", "--warmup", "50", "--cpu-seconds", "3", "--full"])
     assert d["unit"] == "samples/s" and d["n_gpus"] == 1 and d["steps"] == 400 and d["dtype"] == "f32" and d["vs_baseline"] is None
     assert d["config"]["params"] == 5252 and d["config"]["batch"] == 20 and "sinc" in d["config"]["workload"]
     m = d["modes_samples_per_s"]
@@ -44,7 +44,7 @@ def test_sinc_bnn_workload_is_configs_1(gpu):
 def test_default_workload_line_at_n1(gpu):
     """The headline line (configs[2]) at N = 1 with the driver's arguments: contract fields, the roofline of the timed launches,
     and no N > 1 fields."""
-    d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-update-only", "--no-cpu-baseline"])
+    d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-update-only", "--no-cpu-baseline", "--full"])
     assert d["metric"].startswith("MCMC samples/sec") and d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5
     assert d["config"]["params"] == 10002434 and d["config"]["batch"] == 256 and d["scaling"] == "weak" and d["dtype"] == "f32"
     assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 0.01 * d["value"] and d["value"] > 1000
@@ -150,3 +150,25 @@ print("RATE", best)
     best = max(_bench(["--gpus", "1", "--steps", "300", "--warmup", "20", "--no-update-only", "--no-cpu-baseline",
                        "--no-product-defaults"])["value"] for _ in range(2))
     assert rate >= 0.90 * best, (rate, best)       # (process-to-process spread on one box: +-4 % each)
+
+
+@pytest.mark.timeout(900)
+def test_plain_line_is_the_headline_and_dumps_the_last_step(gpu, tmp_path):
+    """Without --full the line is the headline alone (nothing measured after the timed region); --steps is the number of timed
+    steps; --dump-outputs writes what the last timed step handed its caller: every parameter tensor of the sample and the cost."""
+    import numpy as np
+    out = tmp_path / "dump"
+    d = _bench(["--gpus", "1", "--steps", "30", "--warmup", "5", "--dump-outputs", str(out)])
+    assert d["steps"] == 30 and d["warmup"] == 5 and d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 0.01 * d["value"] and d["roofline"]["launches_timed"] == 5
+    for key in ("roofline_unoverlapped", "step_breakdown_us", "chains_per_gpu", "update_only", "roofline_hbm_resident",
+                "cpu_baseline", "value_product_defaults"):
+        assert key not in d, key
+    assert "every_launch_loop" not in d["roofline"]
+    names = sorted(os.listdir(str(out)))
+    assert names == ["cost.npy"] + ["sample_%02d.npy" % k for k in range(9)], names
+    sample = [np.load(str(out / ("sample_%02d.npy" % k))) for k in range(9)]
+    assert [a.shape for a in sample] == [(784, 2048), (2048,), (2048, 2048), (2048,), (2048, 2048), (2048,), (2048, 1), (1,), (1, 1)]
+    assert sum(a.size for a in sample) == d["config"]["params"] and all(a.dtype == np.float32 and np.isfinite(a).all() for a in sample)
+    assert sum(os.path.getsize(str(out / n)) for n in names) <= 64_000_000
+    assert np.isfinite(np.load(str(out / "cost.npy"))).all()

@@ -203,8 +203,9 @@ def test_hip_graph_capture_of_update_kernel(gpu):
                            step_dev=ctr)
     torch.cuda.current_stream().wait_stream(side)
     theta.zero_(); V.zero_()
+    from pysgmcmc_amd.samplers.base_classes import graph_capture
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+    with graph_capture(g):
         kernels.sghmc_step(theta, V, grad, None, None, None, minv, None, 0.01, 1.0, 0.05, False, seed=4, step=0,
                            step_dev=ctr)
         kernels.counter_add(ctr, 1)

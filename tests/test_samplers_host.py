@@ -395,3 +395,43 @@ def test_every_public_name_of_the_reference_packages_imports_from_the_namesake()
                 assert name in module.__all__, "pysgmcmc_amd.%s.__all__ lacks %s" % (package, name)
     from pysgmcmc_amd.models import weight_prior_log_like, log_variance_prior_log_like       # the import a user of the reference writes
     assert callable(weight_prior_log_like) and callable(log_variance_prior_log_like)
+
+
+def test_graph_capture_collects_first_and_keeps_the_collector_off_while_capturing(monkeypatch):
+    """A cyclic collection inside a hipGraph capture may finalise an earlier sampler's graphs, whose memory pool the capturing
+    thread must not release: graph_capture collects dead cycles before the capture and keeps the collector off during it."""
+    import contextlib
+    import gc
+    import weakref
+    from pysgmcmc_amd.samplers import base_classes
+    seen = []
+
+    class Cycle(object):
+        pass
+
+    dead = Cycle()
+    dead.self = dead
+    gone = weakref.ref(dead)
+    del dead
+
+    @contextlib.contextmanager
+    def fake_graph(graph, **kwargs):
+        seen.append(("enter", gone() is None, gc.isenabled(), kwargs))
+        yield
+        seen.append(("exit", gc.isenabled()))
+
+    monkeypatch.setattr(torch.cuda, "graph", fake_graph)
+    was = gc.isenabled()
+    try:
+        gc.enable()
+        with base_classes.graph_capture(object(), capture_error_mode="thread_local"):
+            assert not gc.isenabled()
+        assert gc.isenabled()
+        assert seen == [("enter", True, False, {"capture_error_mode": "thread_local"}), ("exit", False)]
+        gc.disable()                                       # a caller that keeps the collector off keeps it off
+        with pytest.raises(RuntimeError):
+            with base_classes.graph_capture(object()):
+                raise RuntimeError("capture failed")
+        assert not gc.isenabled()
+    finally:
+        (gc.enable if was else gc.disable)()

@@ -13,31 +13,31 @@ done
 PMC_KERNEL_SOURCE_HASH=$(cat $O/kernel_source_hash.txt) python3 tools/pmc_traffic.py profiles/${R}_pmc_traffic $O/pmc_10002434 $O/pmc_49826818 > $O/pmc_traffic.log 2>&1
 cp profiles/${R}_pmc_traffic.json $O/pmc_traffic.json; cp profiles/${R}_pmc_traffic.md $O/pmc_traffic.md
 # (2) the driver's command, twice, the long forms, configs[4]'s and configs[1]'s workloads
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd_a.json 2> $O/bench.err
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd_b.json 2>> $O/bench.err
-python3 bench.py > $O/bench_default.json 2>> $O/bench.err
-python3 bench.py --steps 2000 --warmup 20 --no-cpu-baseline --no-update-only > $O/bench_2000.json 2>> $O/bench.err
-python3 bench.py --chains-per-gpu 2 --steps 200 --warmup 20 --no-cpu-baseline --no-update-only > $O/bench_2chains_per_gpu.json 2>> $O/bench.err
-python3 bench.py --workload bnn50m-sgld --steps 100 --warmup 10 > $O/bench_50m_sgld.json 2>> $O/bench.err
-python3 bench.py --workload bnn50m-rsghmc --steps 100 --warmup 10 > $O/bench_50m_rsghmc.json 2>> $O/bench.err
-python3 bench.py --workload sinc-bnn --steps 3000 --warmup 100 > $O/bench_sinc_bnn.json 2>> $O/bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd_a.json 2> $O/bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd_b.json 2>> $O/bench.err
+python3 bench.py --full > $O/bench_default.json 2>> $O/bench.err
+python3 bench.py --steps 2000 --warmup 20 --no-cpu-baseline --no-update-only --full > $O/bench_2000.json 2>> $O/bench.err
+python3 bench.py --chains-per-gpu 2 --steps 200 --warmup 20 --no-cpu-baseline --no-update-only --full > $O/bench_2chains_per_gpu.json 2>> $O/bench.err
+python3 bench.py --workload bnn50m-sgld --steps 100 --warmup 10 --full > $O/bench_50m_sgld.json 2>> $O/bench.err
+python3 bench.py --workload bnn50m-rsghmc --steps 100 --warmup 10 --full > $O/bench_50m_rsghmc.json 2>> $O/bench.err
+python3 bench.py --workload sinc-bnn --steps 3000 --warmup 100 --full > $O/bench_sinc_bnn.json 2>> $O/bench.err
 # the reference's default dtype (pysgmcmc/samplers/base_classes.py:25): the f64 chain's line
-python3 bench.py --dtype f64 --steps 100 --warmup 10 > $O/bench_10m_f64.json 2>> $O/bench.err
+python3 bench.py --dtype f64 --steps 100 --warmup 10 --full > $O/bench_10m_f64.json 2>> $O/bench.err
 # N > 1 started WITHOUT a launcher (all ranks on this box's one GPU over gloo: the code path, not xGMI timings)
-BENCH_PRIME_STEADY=60 python3 bench.py --gpus 2 --steps 20 --warmup 5 --backend gloo --all-ranks-on-gpu0 --no-update-only > $O/bench_selflaunch_n2_gloo.json 2>> $O/bench.err
-BENCH_PRIME_STEADY=60 python3 bench.py --gpus 8 --steps 20 --warmup 5 --backend gloo --all-ranks-on-gpu0 --no-update-only > $O/bench_selflaunch_n8_gloo.json 2>> $O/bench.err
+BENCH_PRIME_STEADY=60 python3 bench.py --gpus 2 --steps 20 --warmup 5 --backend gloo --all-ranks-on-gpu0 --no-update-only --full > $O/bench_selflaunch_n2_gloo.json 2>> $O/bench.err
+BENCH_PRIME_STEADY=60 python3 bench.py --gpus 8 --steps 20 --warmup 5 --backend gloo --all-ranks-on-gpu0 --no-update-only --full > $O/bench_selflaunch_n8_gloo.json 2>> $O/bench.err
 # (3) kernel-trace stats of the bench commands (program directly after --). Under rocprofv3 the HIP runtime initialises before python
 # runs, so what pysgmcmc_amd.configure_for_device_bound_chains() asks of it is exported here
 export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench10m -o b -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-update-only --no-product-defaults > $O/prof_bench10m.json 2> $O/prof_bench10m.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench50m_rsghmc -o b -- python3 bench.py --workload bnn50m-rsghmc --steps 100 --warmup 10 --no-cpu-baseline --no-update-only --no-product-defaults > $O/prof_bench50m_rsghmc.json 2> $O/prof_bench50m_rsghmc.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench50m_sgld -o b -- python3 bench.py --workload bnn50m-sgld --steps 100 --warmup 10 --no-cpu-baseline --no-update-only --no-product-defaults > $O/prof_bench50m_sgld.json 2> $O/prof_bench50m_sgld.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench10m -o b -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-update-only --no-product-defaults --full > $O/prof_bench10m.json 2> $O/prof_bench10m.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench50m_rsghmc -o b -- python3 bench.py --workload bnn50m-rsghmc --steps 100 --warmup 10 --no-cpu-baseline --no-update-only --no-product-defaults --full > $O/prof_bench50m_rsghmc.json 2> $O/prof_bench50m_rsghmc.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench50m_sgld -o b -- python3 bench.py --workload bnn50m-sgld --steps 100 --warmup 10 --no-cpu-baseline --no-update-only --no-product-defaults --full > $O/prof_bench50m_sgld.json 2> $O/prof_bench50m_sgld.err
 unset DEBUG_CLR_GRAPH_PACKET_CAPTURE
 # per-dispatch timelines of the 10 M-parameter step, f32 and f64
 STEPTRACE_OUT=$O/steptrace bash tools/gpu/step_trace.sh > $O/step_timeline.txt 2>&1
 STEPTRACE_ARGS="--dtype f64" STEPTRACE_OUT=$O/steptrace_f64 bash tools/gpu/step_trace.sh > $O/step_timeline_f64.txt 2>&1
 cd /tmp 2>/dev/null; cd "$GRAFT_REPO_ROOT"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sinc -o b -- python3 bench.py --workload sinc-bnn --steps 3000 --warmup 100 --no-cpu-baseline > $O/prof_sinc.json 2> $O/prof_sinc.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sinc -o b -- python3 bench.py --workload sinc-bnn --steps 3000 --warmup 100 --no-cpu-baseline --full > $O/prof_sinc.json 2> $O/prof_sinc.err
 # keep only the small summaries (the per-dispatch traces are MBs)
 find $O -name "*kernel_trace.csv" -delete
 find $O -name "*counter_collection.csv" -delete
