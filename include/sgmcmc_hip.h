@@ -451,7 +451,7 @@ int sgmcmc_bias_tanh_rowdot_f32(float *a, const float *bias, const float *w, siz
 int sgmcmc_bias_tanh_rowdot_f64(double *a, const double *bias, const double *w, size_t rows, size_t cols, double *out,
                                 const void *stats_ws, double *tsq_parts, sgmcmc_stream_t stream);
 /* Hidden-layer activation (bayesian_neural_network.py:28-56, fully_connected with tanh): a[rows][cols] =
- * tanh(a + bias[c]) in place.                                                                                    */
+ * tanh(a + bias[c]) in place. At most 2^32 - 2^24 elements (rows * cols; 32-bit indices), else SGMCMC_EINVAL. */
 int sgmcmc_bias_tanh_f32(float *a, const float *bias, size_t rows, size_t cols, sgmcmc_stream_t stream);
 int sgmcmc_bias_tanh_f64(double *a, const double *bias, size_t rows, size_t cols, sgmcmc_stream_t stream);
 

@@ -356,7 +356,8 @@ __device__ __forceinline__ double tanh_dev(double x) { return tanh(x); }
 template <typename T>
 __global__ void __launch_bounds__(256) bias_tanh_kernel(T *__restrict__ a, const T *__restrict__ bias, unsigned rows, unsigned cols)
 {
-    // 32-bit indices (the host checks rows * cols < 2^32): a 64-bit modulo per quad would cost more than the tanh
+    // 32-bit indices (the host checks rows * cols <= 2^32 - 2^24, so i + G cannot wrap): a 64-bit modulo per quad would cost
+    // more than the tanh
     const unsigned G = gridDim.x * blockDim.x, gid = blockIdx.x * blockDim.x + threadIdx.x;
     const bool vec = (cols % 4 == 0) && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bias)) % (4 * sizeof(T)) == 0);
     if (vec) {
@@ -1021,7 +1022,9 @@ SGMCMC_WINDOW_GATHER(f64, double)
     {                                                                                                                \
         if (rows == 0 || cols == 0) return 0;                                                                        \
         if (!a || !bias) return fail(SGMCMC_EINVAL, "bias_tanh: NULL argument");                                     \
-        if (rows * cols >= 0xffffffffull) return fail(SGMCMC_EINVAL, "bias_tanh: more than 2^32 - 1 elements");      \
+        /* the scalar path steps a 32-bit index by up to 2^24 lanes: beyond 2^32 - 2^24 elements it would wrap */    \
+        if (rows > (0x100000000ull - 0x1000000ull) / cols)                                                           \
+            return fail(SGMCMC_EINVAL, "bias_tanh: more than 2^32 - 2^24 elements");                                 \
         const size_t lanes = (rows * cols + 3) / 4, blocks = (lanes + 255) / 256;                                    \
         hipLaunchKernelGGL((bias_tanh_kernel<T>), dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,   \
                            static_cast<hipStream_t>(stream), a, bias, (unsigned)rows, (unsigned)cols);               \
