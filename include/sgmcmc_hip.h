@@ -322,6 +322,11 @@ int sgmcmc_moments_update_f64(const double *theta, double *mean, double *m2, siz
  *   finish: on [S_mean | S_sq | S_var] with row pitch ld, n valid elements:
  *           rhat[i] = sqrt(((W (cnt-1)/cnt) + B/cnt) / W), W = S_var/m, B = cnt (S_sq - S_mean^2/m)/(m-1);
  *           one IEEE rounding per operation in the dtype.
+ * Precision: B is formed as a difference of sums (S_sq - S_mean^2/m), which cancels once |mean| is large against the
+ * chains' spread. The _f32 pair loses B from |mean|/sd ~ 1e3 (within-chain sd; R-hat off by ~0.2 there, NaN near 1e4);
+ * the _f64 pair holds to about |mean|/sd ~ 1e5 (R-hat error ~1e-10 at 1e3, ~5e-8 at 1e4). The library's own exchange
+ * (pysgmcmc_amd.diagnostics: cross_chain_rhat, RhatExchange) therefore never uses the _f32 pair: it up-casts f32
+ * moments to f64, packs, reduces and finishes in f64 and rounds R-hat to f32 once.
  * summary_out4 / summary_ws (both NULL or both given; ws = sgmcmc_summary_workspace_bytes()):
  * the K6 summary {sum, sum of squares, min, max} of rhat is left in DEVICE memory on the same
  * stream -- the in-loop exchange never synchronises with the host.                              */
@@ -336,7 +341,8 @@ int sgmcmc_rhat_finish_f64(const double *sum3, size_t n, size_t ld, int m_chains
 
 /* K6 -- deterministic summary of an array: out4 (device, 4 doubles) = {sum, sum of
  * squares, min, max}. Wave-shuffle partial sums -> LDS -> per-block partials in
- * `workspace` -> fixed-order final pass; bit-reproducible for a given n.
+ * `workspace` -> fixed-order final pass; bit-reproducible for a given n. min and max are
+ * NaN exactly when some element is NaN; n = 0 gives {0, 0, +inf, -inf} (x may then be NULL).
  * workspace must hold sgmcmc_summary_workspace_bytes() bytes (device).
  * Used for the adapted-preconditioner (minv) statistics at the end of burn-in and
  * for max/mean R-hat.                                                               */

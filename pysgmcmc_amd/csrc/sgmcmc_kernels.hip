@@ -81,12 +81,17 @@ constexpr int SUMMARY_THREADS = 256;
 
 struct Summary { double s, ss, mn, mx; };
 
+// min / max that propagate NaN whichever side holds it (a bare `a < b ? a : b` drops a NaN in b), so the summary's min
+// and max are NaN exactly when some element is, in any reduction order; on numbers they pick what the bare form picks
+__device__ __forceinline__ double min_nan(double a, double b) { return (a < b || a != a) ? a : b; }
+__device__ __forceinline__ double max_nan(double a, double b) { return (a > b || a != a) ? a : b; }
+
 __device__ __forceinline__ Summary summary_combine(Summary a, Summary b)
 {
     Summary o;
     o.s = a.s + b.s; o.ss = a.ss + b.ss;
-    o.mn = a.mn < b.mn ? a.mn : b.mn;
-    o.mx = a.mx > b.mx ? a.mx : b.mx;
+    o.mn = min_nan(a.mn, b.mn);
+    o.mx = max_nan(a.mx, b.mx);
     return o;
 }
 __device__ __forceinline__ Summary summary_wave_reduce(Summary v)
@@ -126,8 +131,8 @@ __global__ void __launch_bounds__(SUMMARY_THREADS) summary_partial(const T *__re
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += G) {
         double v = (double)x[i];
         acc.s += v; acc.ss += v * v;
-        acc.mn = v < acc.mn ? v : acc.mn;
-        acc.mx = v > acc.mx ? v : acc.mx;
+        acc.mn = min_nan(v, acc.mn);
+        acc.mx = max_nan(v, acc.mx);
     }
     acc = summary_block_reduce(acc);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
@@ -738,7 +743,8 @@ __global__ void window_gather_kernel(const T *__restrict__ X, const T *__restric
 template <typename T>
 int summary(const T *x, size_t n, double *out4, void *ws, hipStream_t st)
 {
-    if (!x || !out4 || !ws) return fail(SGMCMC_EINVAL, "summary: NULL argument");
+    // n = 0 reads nothing (an empty tensor may hand over NULL) and leaves the identities {0, 0, +inf, -inf}
+    if ((!x && n) || !out4 || !ws) return fail(SGMCMC_EINVAL, "summary: NULL argument");
     size_t want = (n + SUMMARY_THREADS - 1) / SUMMARY_THREADS;
     int blocks = (int)(want < (size_t)SUMMARY_BLOCKS ? (want ? want : 1) : SUMMARY_BLOCKS);
     Summary *part = static_cast<Summary *>(ws);

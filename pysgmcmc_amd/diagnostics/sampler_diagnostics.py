@@ -9,7 +9,7 @@ processes, one per GPU, and the ONLY communication on the whole path is the
 R-hat exchange below:
 
   per chain  : Welford running mean / M2 of theta          (K4, 20 B/param/update)
-  exchange   : pack [mean, mean^2, var] -> ONE all-reduce(SUM) of 3P floats over
+  exchange   : pack [mean, mean^2, var] -> ONE all-reduce(SUM) of 3P doubles over
                RCCL/xGMI -> every rank finishes R-hat locally (+ K6 summary)
   ESS        : needs lagged history, so it is computed on thinned, low-dimensional
                traces (cost + a few coordinates): all_gather of (n_kept x K) floats.
@@ -17,6 +17,14 @@ R-hat exchange below:
 ``torch.distributed`` is the transport (backend "nccl" = RCCL on ROCm, "gloo" in
 the CPU tests); with no process group the functions work on a single chain or on
 explicitly passed per-chain moments.
+
+The exchange carries f64 rows whatever the moments' dtype. B is formed as a difference of
+sums (S_sq - S_mean^2/m), which cancels once |mean| is large against the chains' spread:
+in f32 R-hat is off by ~0.2 from |mean| ~ 1e3 within-chain sd on (NaN near 1e4), a scale BNN
+weights reach late in a chain, while f64 holds to ~1e5. So f32 moments are up-cast (exact)
+before the f64 pack, reduced and finished in f64, and R-hat is rounded to f32 once. That
+doubles the bytes of an f32 collective (its RCCL time at N > 1 has never been measured) and
+adds two f64 copies of mean and M2 per exchange.
 """
 import math
 
@@ -32,6 +40,28 @@ __all__ = ["ChainMoments", "cross_chain_rhat", "RhatExchange", "RhatSummary", "S
 def _dist():
     import torch.distributed as dist
     return dist if (dist.is_available() and dist.is_initialized()) else None
+
+
+def _pack_f64(moments, out3, n_shards=1, shard_len=None, up=None):
+    """This chain's f64 rows ``[mean | mean^2 | var]`` into ``out3`` (float64): f32 moments go through ``up``, a
+    float64 ``(2, n)`` scratch (allocated when None), so the pack kernel sees them exactly."""
+    mean, m2 = moments.mean, moments.m2
+    if mean.dtype != torch.float64:
+        if up is None:
+            up = torch.empty(2, moments.n, dtype=torch.float64, device=mean.device)
+        up[0].copy_(mean)
+        up[1].copy_(m2)
+        mean, m2 = up[0], up[1]
+    kernels.rhat_pack(mean, m2, moments.count, out3, n_shards, shard_len)
+
+
+def _finish_f64(sum3, n, m, count, rhat, rhat64, summary=None, ld=None):
+    """R-hat of ``n`` parameters from the f64 chain sums into ``rhat`` (its dtype): computed in ``rhat64`` (float64) and
+    rounded once when ``rhat`` is f32. The K6 summary, if asked for, is that of the f64 R-hat."""
+    out4, ws = (None, None) if summary is None else (summary.out4, summary.workspace)
+    kernels.rhat_finish(sum3, n, m, count, rhat64, out4, ws, ld=ld)
+    if rhat64 is not rhat:
+        rhat[:n].copy_(rhat64[:n])
 
 
 class ChainMoments(object):
@@ -81,9 +111,10 @@ class RhatSummary(object):
 def cross_chain_rhat(moments, group=None, pack=None, rhat=None, with_summary=True):
     """R-hat of every parameter across the chains of the process group.
 
-    One all-reduce of ``3 * n`` elements in the moments' dtype. All ranks must call with the same
-    ``moments.count``. Returns ``(rhat, summary)`` with ``summary = {"mean", "max"}``
-    (python floats; forces a sync) or ``None`` when ``with_summary`` is False.
+    One all-reduce of ``3 * n`` float64 elements, whatever the moments' dtype (``pack``, if given, is float64;
+    see the module docstring). All ranks must call with the same ``moments.count``. Returns ``(rhat, summary)``
+    with ``rhat`` in the moments' dtype and ``summary = {"mean", "max"}`` (python floats; forces a sync) or
+    ``None`` when ``with_summary`` is False.
     """
     dist = _dist()
     if dist is None:
@@ -94,17 +125,15 @@ def cross_chain_rhat(moments, group=None, pack=None, rhat=None, with_summary=Tru
     n = moments.n
     dt, dev = moments.mean.dtype, moments.mean.device
     if pack is None:
-        pack = torch.empty(3 * n, dtype=dt, device=dev)
+        pack = torch.empty(3 * n, dtype=torch.float64, device=dev)
     if rhat is None:
         rhat = torch.empty(n, dtype=dt, device=dev)
-    kernels.rhat_pack(moments.mean, moments.m2, moments.count, pack)
+    rhat64 = rhat if rhat.dtype == torch.float64 else torch.empty(n, dtype=torch.float64, device=dev)
+    _pack_f64(moments, pack)
     dist.all_reduce(pack, group=group)
-    if not with_summary:
-        kernels.rhat_finish(pack, n, world, moments.count, rhat)
-        return rhat, None
-    summ = RhatSummary(n, dev)
-    kernels.rhat_finish(pack, n, world, moments.count, rhat, summ.out4, summ.workspace)
-    return rhat, summ.as_dict()
+    summ = RhatSummary(n, dev) if with_summary else None
+    _finish_f64(pack, n, world, moments.count, rhat, rhat64, summ)
+    return rhat, (summ.as_dict() if with_summary else None)
 
 
 class _NoCollective(object):
@@ -115,13 +144,14 @@ class _NoCollective(object):
 
 
 class RhatExchange(object):
-    """Non-blocking form of :func:`cross_chain_rhat`: ``start`` packs a snapshot of the moments and
+    """Non-blocking form of :func:`cross_chain_rhat`: ``start`` packs a snapshot of the moments (f64 rows for either
+    ``dtype``, see the module docstring; ``exchange.rhat`` is in ``dtype``) and
     issues the collective asynchronously on RCCL's own stream, sampling continues, ``finish`` waits
     (stream-level) for it and computes R-hat. The snapshot buffer is private, so the chain may
     keep updating its moments in between (overlaps the only collective of the path with compute).
 
     ``mode``:
-      * ``"allreduce"``: ONE all-reduce(SUM) of ``3 n`` elements; every rank finishes all ``n`` parameters and holds
+      * ``"allreduce"``: ONE all-reduce(SUM) of ``3 n`` f64 elements; every rank finishes all ``n`` parameters and holds
         the full R-hat vector (``exchange.rhat``). Per rank ``6 n (m-1)/m`` elements cross xGMI.
       * ``"reduce_scatter"`` (reduce-scatter + all-gather): the pack is laid out in ``m`` parameter
         shards, ONE reduce-scatter(SUM) leaves on rank ``r`` the summed rows of shard ``r`` (``3 n (m-1)/m`` elements
@@ -142,6 +172,9 @@ class RhatExchange(object):
     def __init__(self, n, device, group=None, dtype=torch.float32, mode="allreduce"):
         assert mode in ("allreduce", "reduce_scatter")
         self.n = int(n)
+        self.dtype = dtype
+        # f32 moments: exact f64 copies of mean and M2 for the pack (reused by every local chain, stream-ordered)
+        self._up = None if dtype == torch.float64 else torch.empty(2, self.n, dtype=torch.float64, device=device)
         self.group = group
         self.mode = mode
         self.exchanges = 0
@@ -151,9 +184,10 @@ class RhatExchange(object):
         self._pack_more = None
         if mode == "allreduce":
             self.n_shards, self.shard_len, self.n_valid, self.rank = 1, self.n, self.n, 0
-            self.pack = torch.empty(3 * self.n, dtype=dtype, device=device)
+            self.pack = torch.empty(3 * self.n, dtype=torch.float64, device=device)
             self.shard_sum = self.pack
             self.rhat = torch.empty(self.n, dtype=dtype, device=device)
+            self._rhat64 = self.rhat if dtype == torch.float64 else torch.empty(self.n, dtype=torch.float64, device=device)
             self.summary = RhatSummary(self.n, device)
             return
         dist = _dist()
@@ -168,9 +202,10 @@ class RhatExchange(object):
             raise ValueError("RhatExchange: fewer parameters (%d) than chains (%d)" % (self.n, m))
         self.n_shards, self.shard_len = m, L
         self.n_valid = max(0, min(L, self.n - self.rank * L))
-        self.pack = torch.empty(3 * m * L, dtype=dtype, device=device)
-        self.shard_sum = torch.empty(3 * L, dtype=dtype, device=device)
+        self.pack = torch.empty(3 * m * L, dtype=torch.float64, device=device)
+        self.shard_sum = torch.empty(3 * L, dtype=torch.float64, device=device)
         self.rhat = torch.empty(L, dtype=dtype, device=device)     # this rank's shard of R-hat (first n_valid entries)
+        self._rhat64 = self.rhat if dtype == torch.float64 else torch.empty(L, dtype=torch.float64, device=device)
         self.summary = ShardedRhatSummary(self.n, m, device, group)
         # gloo (CPU tests, single-GPU rehearsals) has no reduce-scatter: all-reduce the pack, keep the own chunk
         self._native_rs = str(dist.get_backend(group)).lower() == "nccl"
@@ -184,10 +219,10 @@ class RhatExchange(object):
         if not local:
             raise ValueError("RhatExchange.start: no moments")
         for mom in local:
-            if mom.mean.dtype != self.pack.dtype:
-                # the pack kernel is chosen from the moments' dtype: an f64 pack into this f32 buffer would overrun it
+            if mom.mean.dtype != self.dtype:
+                # R-hat is handed back in the exchange's dtype; moments of another dtype are refused
                 raise TypeError("RhatExchange was built for %s but the chain's moments are %s: pass dtype=%s" % (
-                    self.pack.dtype, mom.mean.dtype, mom.mean.dtype))
+                    self.dtype, mom.mean.dtype, mom.mean.dtype))
         if any(mom.count != local[0].count for mom in local):
             raise ValueError("RhatExchange.start: the local chains' moments hold different sample counts")
         dist = _dist()
@@ -196,11 +231,11 @@ class RhatExchange(object):
             raise RuntimeError("RhatExchange needs >= 2 chains: an initialised process group with >= 2 ranks, or (mode="
                                "'allreduce') several local chains")
         assert not self.pending, "finish() the previous exchange first"
-        kernels.rhat_pack(local[0].mean, local[0].m2, local[0].count, self.pack, self.n_shards, self.shard_len)
+        _pack_f64(local[0], self.pack, self.n_shards, self.shard_len, self._up)
         for mom in local[1:]:                 # the pack is additive over chains: local chains are summed before the collective
             if self._pack_more is None:
                 self._pack_more = torch.empty_like(self.pack)
-            kernels.rhat_pack(mom.mean, mom.m2, mom.count, self._pack_more, self.n_shards, self.shard_len)
+            _pack_f64(mom, self._pack_more, self.n_shards, self.shard_len, self._up)
             self.pack.add_(self._pack_more)
         self._count = local[0].count
         self._local_chains = len(local)
@@ -220,8 +255,7 @@ class RhatExchange(object):
         if self.mode == "reduce_scatter" and not self._native_rs:
             L3 = 3 * self.shard_len
             self.shard_sum.copy_(self.pack[self.rank * L3:(self.rank + 1) * L3])
-        kernels.rhat_finish(self.shard_sum, self.n_valid, m, self._count, self.rhat,
-                            self.summary.out4, self.summary.workspace, ld=self.shard_len)
+        _finish_f64(self.shard_sum, self.n_valid, m, self._count, self.rhat, self._rhat64, self.summary, ld=self.shard_len)
         if self.mode == "reduce_scatter":
             self.summary.combine()            # all-gather of 4 doubles per rank, still no host synchronisation
         self.exchanges += 1
