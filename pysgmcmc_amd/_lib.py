@@ -27,8 +27,9 @@ def build(force=False):
     """Compile ``csrc/libsgmcmc_hip.so`` for gfx950 with hipcc (no GPU needed)."""
     import subprocess
     deps = [os.path.join(_CSRC, f) for f in ("sgmcmc_kernels.hip", "sgmcmc_sghmc.hip", "sgmcmc_sgld.hip", "sgmcmc_rsghmc.hip", "sgmcmc_toy.hip", "sgmcmc_bnn_gemm.hip", "sgmcmc_stream.hpp", "sgmcmc_bnn_fused.hip", "sgmcmc_svgd.hip", "sgmcmc_device.hpp",
-                                             "sgmcmc_host.hpp")]
+                                             "sgmcmc_host.hpp", "sgmcmc_ess.hip")]
     deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip.h"))
+    deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip_diag.h"))
     stale = (not os.path.exists(_LIB_PATH)
              or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(d) for d in deps))
     if force or stale:
@@ -38,6 +39,9 @@ def build(force=False):
 
 _lib = None
 ABI_VERSION = 6               # SGMCMC_ABI_VERSION of include/sgmcmc_hip.h
+DIAG_ABI_VERSION = 1          # SGMCMC_DIAG_ABI_VERSION of include/sgmcmc_hip_diag.h (the diagnostics add-on)
+ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
+ESS_MAX_CHAINS = 64
 
 _u64 = ctypes.c_uint64
 _sz = ctypes.c_size_t
@@ -187,6 +191,12 @@ def _declare(lib):
     lib.sgmcmc_step_stats_records.restype = _sz
     lib.sgmcmc_step_stats_finish.argtypes = [_vp, _vp, _vp]
     lib.sgmcmc_step_stats_finish.restype = _ci
+    # include/sgmcmc_hip_diag.h
+    lib.sgmcmc_diag_abi_version.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_ess_variogram_" + sfx)
+        f.argtypes = [ctypes.POINTER(_vp), _ci, _sz, _sz, _sz, _vp, _vp, _vp, _ci, _lp, _vp]
+        f.restype = _ci
 
 
 def lib():
@@ -205,6 +215,8 @@ def lib():
     _declare(handle)
     if handle.sgmcmc_abi_version() != ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_diag_abi_version() != DIAG_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: diagnostics ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

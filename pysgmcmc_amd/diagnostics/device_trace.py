@@ -1,0 +1,188 @@
+"""Device-resident traces of whole parameter vectors, and the effective sample size of EVERY parameter from them.
+
+The reference's ``effective_sample_sizes`` (``pysgmcmc/diagnostics/sampler_diagnostics.py:47-82``) returns one ESS
+per parameter dimension from traces that are Python lists of host arrays; ``sampler_diagnostics.effective_n`` restates
+its estimator for ONE scalar (an FFT and a host read per call). Here the trace never leaves the device:
+
+  ``DeviceTrace``                 a preallocated ``(capacity, n_params)`` matrix; ``append`` is one stream-ordered
+                                  device copy, ``record`` steps a sampler and keeps its flat ``theta`` row
+  ``effective_n_all``             one launch of K10 (``kernels.ess_variogram``) -> int64 ESS of all P parameters, on the
+                                  device, no host synchronisation
+  ``effective_sample_sizes_of``   the reference's ``{name: array shaped like the parameter}`` cut from that vector
+
+Scope: chains that share a device (``ConcurrentChains``, sequential chains as in ``multitrace``, the stacked state of
+``FusedBNNChains``) and a single chain. Chains on different ranks are OUT of scope: the stop rule needs the cross-chain
+``rho_t`` lag by lag, so an all-parameter ESS across ranks would take a collective per lag or an all-gather of whole
+traces; ``sampler_diagnostics.ess_across_ranks`` stays the multi-rank path, for a few scalars.
+"""
+import torch
+
+from pysgmcmc_amd import kernels
+
+__all__ = ["DeviceTrace", "effective_n_all", "effective_sample_sizes_of"]
+
+
+class DeviceTrace(object):
+    """``capacity`` samples of an ``n_params``-long parameter vector in one preallocated device matrix."""
+
+    def __init__(self, n_params, capacity, device, dtype=torch.float32):
+        self.n_params = int(n_params)
+        self.capacity = int(capacity)
+        if self.n_params < 0 or self.capacity < 0:
+            raise ValueError("DeviceTrace: n_params and capacity must be >= 0")
+        self.buffer = torch.empty(self.capacity, self.n_params, dtype=dtype, device=device)
+        self._len = 0
+        # set by record(): how to cut a flat vector into the sampler's parameters
+        self.param_names = None
+        self.param_shapes = None
+        self.param_offsets = None
+
+    @property
+    def device(self):
+        return self.buffer.device
+
+    @property
+    def dtype(self):
+        return self.buffer.dtype
+
+    def __len__(self):
+        return self._len
+
+    def append(self, theta_flat):
+        """Copy one flat parameter vector into the next row (asynchronous on the current stream; no host sync)."""
+        if self._len >= self.capacity:
+            raise IndexError("DeviceTrace: capacity of %d samples exhausted" % self.capacity)
+        if theta_flat.numel() != self.n_params:
+            raise ValueError("DeviceTrace.append: %d elements, the trace is %d wide" % (theta_flat.numel(), self.n_params))
+        self.buffer[self._len].copy_(theta_flat.detach().reshape(-1), non_blocking=True)
+        self._len += 1
+
+    def values(self):
+        """The ``(len, n_params)`` view of the samples recorded so far (aliases the buffer)."""
+        return self.buffer[:self._len]
+
+    def reset(self):
+        self._len = 0
+
+    @classmethod
+    def record(cls, sampler, n_samples, keep_every=1):
+        """Step ``sampler`` ``n_samples * keep_every`` times and keep ``sampler.arena.row("theta")`` after every
+        ``keep_every``-th step. The sampler's ``sample_format`` is ``"view"`` for the duration (no per-step host
+        copy) and restored afterwards, also when a step raises. The chain itself is untouched: the appends only read
+        theta, in stream order after the step that produced it."""
+        n_samples, keep_every = int(n_samples), int(keep_every)
+        if n_samples < 0 or keep_every < 1:
+            raise ValueError("DeviceTrace.record: n_samples must be >= 0 and keep_every >= 1")
+        arena = sampler.arena
+        theta = arena.row("theta")
+        trace = cls(theta.numel(), n_samples, theta.device, theta.dtype)
+        trace.param_names = list(getattr(sampler, "param_names", [str(i) for i in range(len(arena.shapes))]))
+        trace.param_shapes = list(arena.shapes)
+        trace.param_offsets = list(arena.offsets)
+        fmt = sampler.sample_format
+        sampler.sample_format = "view"
+        try:
+            for _ in range(n_samples):
+                for _ in range(keep_every):
+                    next(sampler)
+                trace.append(sampler.arena.row("theta"))
+        finally:
+            sampler.sample_format = fmt
+        return trace
+
+
+def _chain_matrices(traces):
+    """``traces`` of effective_n_all -> list of (n, P) tensors, one per chain."""
+    if isinstance(traces, DeviceTrace):
+        return [traces.values()]
+    if torch.is_tensor(traces):
+        if traces.dim() == 2:
+            return [traces]
+        if traces.dim() == 3:
+            return list(traces.unbind(0))
+        raise ValueError("effective_n_all: a tensor of traces must be (n, P) or (m, n, P), got %s" % (tuple(traces.shape),))
+    try:
+        items = list(traces)
+    except TypeError:
+        raise TypeError("effective_n_all: traces must be a DeviceTrace, a sequence of them or a device tensor")
+    if not items:
+        raise ValueError("effective_n_all: no traces")
+    mats = []
+    for t in items:
+        if isinstance(t, DeviceTrace):
+            mats.append(t.values())
+        elif torch.is_tensor(t) and t.dim() == 2:
+            mats.append(t)
+        else:
+            raise TypeError("effective_n_all: every chain must be a DeviceTrace or an (n, P) tensor")
+    first = mats[0]
+    for x in mats[1:]:
+        if x.shape[0] != first.shape[0]:
+            raise ValueError("effective_n_all: the chains hold different numbers of samples (%d and %d)" % (first.shape[0], x.shape[0]))
+        if x.shape[1] != first.shape[1]:
+            raise ValueError("effective_n_all: the chains are of different widths (%d and %d)" % (first.shape[1], x.shape[1]))
+    return mats
+
+
+def effective_n_all(traces, details=False, staging="auto", launch=None):
+    """Effective sample size of each of the P parameters (variogram estimate, the arithmetic of
+    ``sampler_diagnostics.effective_n``) in ONE kernel launch on the traces' device.
+
+    ``traces``: a ``DeviceTrace`` (one chain), a sequence of them (one per chain; equal lengths and widths, else
+    ``ValueError``), or a device tensor ``(n, P)`` / ``(m, n, P)``. At most 64 chains, at least 2 samples each.
+    Returns the int64 device tensor of P values; with ``details=True`` the tuple ``(ess, raw, stop_lag)``: the
+    untruncated float64 estimate and the lag T at which each parameter's sum stopped. A parameter whose traces are
+    constant (Vhat = 0) gets ``ess = 0``, ``raw = NaN``, ``stop_lag = 1`` where the scalar function raises. Nothing here
+    waits for the host. Chains on different ranks are out of scope (see the module docstring)."""
+    mats = _chain_matrices(traces)
+    first = mats[0]
+    if first.shape[0] < 2:
+        raise ValueError("effective_n_all: needs at least 2 samples per chain, got %d" % first.shape[0])
+    if len(mats) > 64:
+        raise ValueError("effective_n_all: at most 64 chains, got %d" % len(mats))
+    P, dev = int(first.shape[1]), first.device
+    ess = torch.empty(P, dtype=torch.int64, device=dev)
+    raw = torch.empty(P, dtype=torch.float64, device=dev) if details else None
+    stop = torch.empty(P, dtype=torch.int32, device=dev) if details else None
+    kernels.ess_variogram(mats, ess, raw, stop, staging=staging, launch=launch)
+    return (ess, raw, stop) if details else ess
+
+
+def effective_sample_sizes_of(samplers_or_traces, param_shapes=None, names=None):
+    """ESS per parameter dimension, ``{name: int64 device tensor shaped like the parameter}``: what the reference's
+    ``effective_sample_sizes`` returns, from device traces.
+
+    ``samplers_or_traces``: what :func:`effective_n_all` accepts. Traces made by ``DeviceTrace.record`` know their
+    sampler's parameter shapes and ``param_names``; otherwise pass ``param_shapes`` (dense, in order) and optionally
+    ``names`` (default ``"0", "1", ...`` as the samplers name their parameters)."""
+    src = samplers_or_traces
+    probe = src if isinstance(src, DeviceTrace) else (src[0] if isinstance(src, (list, tuple)) and src else None)
+    offsets = None
+    if param_shapes is None:
+        if not isinstance(probe, DeviceTrace) or probe.param_shapes is None:
+            raise ValueError("effective_sample_sizes_of: param_shapes is needed unless the traces come from DeviceTrace.record")
+        param_shapes, offsets = probe.param_shapes, probe.param_offsets
+        if names is None:
+            names = probe.param_names
+    shapes = [tuple(s) for s in param_shapes]
+    sizes = []
+    for shp in shapes:
+        k = 1
+        for d in shp:
+            k *= int(d)
+        sizes.append(k)
+    if offsets is None:
+        offsets, off = [], 0
+        for k in sizes:
+            offsets.append(off)
+            off += k
+    if names is None:
+        names = [str(i) for i in range(len(shapes))]
+    names = list(names)
+    if len(names) != len(shapes):
+        raise ValueError("effective_sample_sizes_of: %d names for %d parameters" % (len(names), len(shapes)))
+    ess = effective_n_all(src)
+    if offsets and offsets[-1] + sizes[-1] > ess.numel():
+        raise ValueError("effective_sample_sizes_of: the parameters hold %d elements, the traces are %d wide" % (
+            offsets[-1] + sizes[-1], ess.numel()))
+    return {name: ess[o:o + k].view(shp) for name, o, k, shp in zip(names, offsets, sizes, shapes)}

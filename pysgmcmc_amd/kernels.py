@@ -17,6 +17,7 @@ __all__ = [
     "moments_update", "rhat_pack", "rhat_finish", "summary",
     "LaunchConfig", "KernelEvents", "StepOpts", "step_stats_records", "step_scalars", "toy_chains", "set_launch_config", "get_launch_config", "summary_workspace", "counter_add", "StepStats", "bnn_head", "bnn_dense_tanh_backward", "bnn_dense_tanh_backward_fits", "colsum_finish", "tanh_backward", "tanh_backward_colsum", "bnn_last_layer_backward", "bnn_fused_sghmc_steps", "step_stats_finish",
     "bnn_fused_sgld_steps", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
+    "ess_variogram",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -396,6 +397,67 @@ def rhat_finish(sum3, n, m_chains, count, rhat, summary_out4=None, summary_works
         rc = f(_ptr(sum3), int(n), ld, int(m_chains), int(count), _ptr(rhat), _ptr(summary_out4), _ptr(summary_workspace),
                _stream(sum3))
     check(rc, "sgmcmc_rhat_finish")
+
+
+_ESS_STAGING = {"auto": 0, "lds": 1, "global": 2}
+
+
+def ess_variogram(chains, ess, raw=None, stop_lag=None, ld=None, staging="auto", launch=None):
+    """K10 (``include/sgmcmc_hip_diag.h``): effective sample size of every parameter from the traces of ``m`` chains.
+
+    ``chains``: one ``(m, n, P)`` device tensor, one ``(n, P)`` tensor (a single chain), or a sequence of ``m``
+    ``(n, P)`` tensors that live in buffers of their own. Rows must be dense (stride 1 along P) and all chains share
+    the row pitch ``ld`` (default: the tensors' own row stride), so views of wider buffers pass without a copy.
+    ``ess``: int64[P]; ``raw``: float64[P] or None; ``stop_lag``: int32[P] or None. ``staging``: ``"auto"``,
+    ``"lds"`` or ``"global"`` (where the slab lives while the lags are walked; same bits). ``launch``: a
+    ``LaunchConfig`` (``block_threads`` = parameters per workgroup, and the timestamp events)."""
+    import ctypes
+    if torch.is_tensor(chains):
+        if chains.dim() == 2:
+            mats = [chains]
+        elif chains.dim() == 3:
+            mats = list(chains.unbind(0))
+        else:
+            raise ValueError("ess_variogram: chains must be (n, P), (m, n, P) or a sequence of (n, P) tensors")
+    else:
+        mats = list(chains)
+    if not mats:
+        raise ValueError("ess_variogram: no chains")
+    first = mats[0]
+    for x in mats:
+        if not x.is_cuda:
+            raise SgmcmcLibraryError("pysgmcmc_amd: trace lives on %s; the effective sample size of all parameters runs "
+                                     "only as a HIP kernel on an AMD GPU (no CPU fallback)." % x.device)
+        if x.dim() != 2 or x.shape != first.shape:
+            raise ValueError("ess_variogram: every chain must be an (n, P) matrix of the same shape")
+        if x.dtype != first.dtype or x.device != first.device:
+            raise TypeError("ess_variogram: the chains must share a dtype and a device")
+    f = getattr(lib(), "sgmcmc_ess_variogram_" + _sfx(first))
+    n, P = int(first.shape[0]), int(first.shape[1])
+    if ld is None:
+        ld = int(first.stride(0)) if n > 1 else P
+    ld = int(ld)
+    for x in mats:
+        if (P > 1 and x.stride(1) != 1) or (n > 1 and x.stride(0) != ld):
+            raise ValueError("ess_variogram: rows must be dense and %d elements apart in every chain" % ld)
+    for out, dt, name in ((ess, torch.int64, "ess"), (raw, torch.float64, "raw"), (stop_lag, torch.int32, "stop_lag")):
+        if out is None:
+            if name == "ess":
+                raise ValueError("ess_variogram: ess is required")
+            continue
+        if out.dtype != dt:
+            raise TypeError("ess_variogram: %s must be %s" % (name, dt))
+        if out.numel() != P or out.device != first.device:
+            raise ValueError("ess_variogram: %s must hold P = %d elements on %s" % (name, P, first.device))
+    try:
+        stage = _ESS_STAGING[staging]
+    except KeyError:
+        raise ValueError("ess_variogram: staging must be 'auto', 'lds' or 'global'")
+    table = (ctypes.c_void_p * len(mats))(*[x.data_ptr() for x in mats])
+    with torch.cuda.device(first.device):
+        rc = f(table, len(mats), n, P, ld, _ptr(ess), _ptr(raw), _ptr(stop_lag), stage, _launch(launch), _stream(first))
+    check(rc, "sgmcmc_ess_variogram")
+    return ess
 
 
 def summary_workspace(device):
