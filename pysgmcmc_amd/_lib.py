@@ -27,9 +27,10 @@ def build(force=False):
     """Compile ``csrc/libsgmcmc_hip.so`` for gfx950 with hipcc (no GPU needed)."""
     import subprocess
     deps = [os.path.join(_CSRC, f) for f in ("sgmcmc_kernels.hip", "sgmcmc_sghmc.hip", "sgmcmc_sgld.hip", "sgmcmc_rsghmc.hip", "sgmcmc_toy.hip", "sgmcmc_bnn_gemm.hip", "sgmcmc_stream.hpp", "sgmcmc_bnn_fused.hip", "sgmcmc_svgd.hip", "sgmcmc_device.hpp",
-                                             "sgmcmc_host.hpp", "sgmcmc_ess.hip")]
+                                             "sgmcmc_host.hpp", "sgmcmc_ess.hip", "sgmcmc_scalars.hpp")]
     deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip.h"))
     deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip_diag.h"))
+    deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip_fused.h"))
     stale = (not os.path.exists(_LIB_PATH)
              or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(d) for d in deps))
     if force or stale:
@@ -40,6 +41,7 @@ def build(force=False):
 _lib = None
 ABI_VERSION = 6               # SGMCMC_ABI_VERSION of include/sgmcmc_hip.h
 DIAG_ABI_VERSION = 1          # SGMCMC_DIAG_ABI_VERSION of include/sgmcmc_hip_diag.h (the diagnostics add-on)
+FUSED_ABI_VERSION = 1         # SGMCMC_FUSED_ABI_VERSION of include/sgmcmc_hip_fused.h (the whole-step add-on)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 
@@ -197,6 +199,21 @@ def _declare(lib):
         f = getattr(lib, "sgmcmc_ess_variogram_" + sfx)
         f.argtypes = [ctypes.POINTER(_vp), _ci, _sz, _sz, _sz, _vp, _vp, _vp, _ci, _lp, _vp]
         f.restype = _ci
+    # include/sgmcmc_hip_fused.h
+    lib.sgmcmc_fused_abi_version.restype = _ci
+    for sfx, real in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        net = [_sz, _sz, _ci, ctypes.POINTER(_ci), _ci, _vp, _vp, _sz, _vp, _ci] + [ctypes.c_double] * 5
+        for kind, n_scalars in (("sghmc", 2), ("sgld", 2), ("rsghmc", 4)):
+            f = getattr(lib, "sgmcmc_%s_scalars_steps_%s" % (kind, sfx))        # host pointers, nothing launched
+            f.argtypes = [ctypes.POINTER(real), _sz] + [real] * n_scalars + [ctypes.POINTER(real)]
+            f.restype = _ci
+        for kind, n_rows in (("sghmc", 7), ("sgld", 6)):
+            f = getattr(lib, "sgmcmc_bnn_fused_%s_sched_steps_%s" % (kind, sfx))
+            f.argtypes = [_vp] * n_rows + net + [_vp, real, real, _u64, _u64, _u64, _u64, _vp, _vp, _vp]
+            f.restype = _ci
+        f = getattr(lib, "sgmcmc_bnn_fused_rsghmc_steps_" + sfx)
+        f.argtypes = [_vp] * 3 + net + [real] * 5 + [_vp, _u64, _u64, _u64, _vp, _vp, _vp]
+        f.restype = _ci
 
 
 def lib():
@@ -217,6 +234,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_diag_abi_version() != DIAG_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: diagnostics ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_fused_abi_version() != FUSED_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: whole-step add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

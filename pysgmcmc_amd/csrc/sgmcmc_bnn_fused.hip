@@ -25,23 +25,32 @@
 // matrix products are plain fp32/fp64 dot products in k order, so a fused chain tracks the
 // GEMM-based path to rounding (tests: 2e-4 relative over 12 steps, like the GEMM path itself
 // against the fp64 golden trajectory).
+//
+// Three update operators (KIND): SGHMC (K1's SghmcOp), preconditioned SGLD (K2's SgldOp) and relativistic SGHMC (K3's
+// RsghmcOp: rows theta, p, grad; no preconditioner rows, no burn-in switch). The operator's five stepsize-derived scalars
+// arrive by value (bnn_fused_sghmc_kernel<T, KIND>: one stepsize for the launch) or from a device table of one block per step
+// (bnn_fused_sghmc_kernel<T, KIND + FUSED_TABLE>: a stepsize schedule inside the launch; include/sgmcmc_hip_fused.h). The
+// table is a template parameter, so the by-value kernels carry no trace of it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
 #include "sgmcmc_hip.h"
+#include "sgmcmc_hip_fused.h"
 
 #pragma clang fp contract(off)
 
 #include "sgmcmc_device.hpp"
 #include "sgmcmc_host.hpp"
+#include "sgmcmc_scalars.hpp"
 
 using namespace sgmcmc_host;
 
 namespace {
 
 constexpr int FUSED_MAX_LAYERS = 8;
+constexpr int FUSED_TABLE = 4;             // bit of the kernel's KIND_ parameter: per-step scalars table
 constexpr int FUSED_THREADS = 512;       // 8 waves: 2 per SIMD, 256 registers each (1024 lanes spilled registers: 24.3 vs 20.4 us per step)
 
 __device__ __forceinline__ float tanh_t(float x) { return tanhf(x); }
@@ -62,7 +71,7 @@ __device__ __forceinline__ void st2(T *p, typename Pair<T>::type v) { *reinterpr
 
 template <typename T>
 struct FusedArgs {
-    T *theta, *V, *grad, *tau, *g, *vh, *minv;          // chain c at + c * chain_stride
+    T *theta, *V, *grad, *tau, *g, *vh, *minv;          // chain c at + c * chain_stride (V: the relativistic kind's p)
     size_t n_params, chain_stride;
     int n_layers;                                        // number of weight layers L
     int sizes[FUSED_MAX_LAYERS + 1];                     // sizes[0] = inputs, sizes[L] = 1
@@ -80,6 +89,9 @@ struct FusedArgs {
     uint64_t first_step, n_steps, burn_in_steps, seed_base;
     const T *xi;                                         // nullable: [n_steps][n_params], chain 0
     T *cost_out;                                         // [n_chains][n_steps]
+    T rs_eps, rs_mass, rs_D, rs_m2c2, rs_nscale, rs_inv; // host-derived scalars of K3 (relativistic chains); rs_inv = 1 / m2c2
+    int rs_pow2;                                         // m2c2 is a power of two: RsghmcOp's POW2 form (by-value launches only)
+    const T *scalars_steps;                              // table kernels: [n_steps][5], the operator's scalars_dev block of step t
 };
 
 // block-wide sum of one double per lane; every lane returns the total. red: 17 doubles of LDS.
@@ -127,10 +139,19 @@ __device__ __forceinline__ double run_update(Op &op, size_t n_params, typename O
     return acc[0];                                        // this lane's share of sum(theta'^2)
 }
 
+// TABLE: the operator reads its five scalars from `srow` (this step's row of FusedArgs::scalars_steps) in prepare(), as a
+// graph-replayed per-step launch reads them from StepOpts.scalars_dev
+template <bool TABLE, typename Op>
+__device__ __forceinline__ double run_update_with(Op &op, const typename Op::real *srow, size_t n_params, typename Op::real *wl)
+{
+    if constexpr (TABLE) { op.scalars_dev = srow; op.prepare(); }
+    return run_update(op, n_params, wl);
+}
+
 // KIND 0: SGHMC (K1's operator, sghmc.py:165-251); KIND 1: preconditioned SGLD (K2's operator, sgld.py:149-211)
-template <typename T, int KIND, bool ADAPT, bool INJECT>
+template <typename T, int KIND, bool TABLE, bool ADAPT, bool INJECT>
 __device__ __forceinline__ double update_phase(const FusedArgs<T> &a, T *theta, T *V, const T *grad, T *tau, T *g, T *vh,
-                                               T *minv, const T *xi, uint64_t seed, uint64_t step, T *wl)
+                                               T *minv, const T *xi, const T *srow, uint64_t seed, uint64_t step, T *wl)
 {
     NoiseKey nk;
     nk.k0 = (uint32_t)seed; nk.k1 = (uint32_t)(seed >> 32);
@@ -139,24 +160,45 @@ __device__ __forceinline__ double update_phase(const FusedArgs<T> &a, T *theta, 
     if (KIND == 0) {
         SghmcOp<T, ADAPT, INJECT> op{theta, V, grad, tau, g, vh, minv, nullptr, xi,
                                      a.eps_e2, a.c1, a.c3, a.e4, a.mdecay, a.grad_decay, nk, nullptr};
-        return run_update(op, a.n_params, wl);
+        return run_update_with<TABLE>(op, srow, a.n_params, wl);
     } else {
         SgldOp<T, ADAPT, INJECT> op{theta, grad, tau, g, vh, minv, nullptr, xi, a.sgld_eps, a.sgld_A, a.sgld_a_eff,
                                     a.sgld_two_eps, a.sgld_den, a.grad_decay, nk, nullptr};
-        return run_update(op, a.n_params, wl);
+        return run_update_with<TABLE>(op, srow, a.n_params, wl);
     }
 }
 
-template <typename T, int KIND>
+// KIND 2: relativistic SGHMC (K3's operator, relativistic_sghmc.py:120-140). K8 leaves d cost / d theta in the gradient row; the
+// operator negates it, as in the per-step launch.
+template <typename T, bool TABLE, bool POW2, bool INJECT>
+__device__ __forceinline__ double update_phase_rsghmc(const FusedArgs<T> &a, T *theta, T *p, const T *grad, const T *xi,
+                                                      const T *srow, uint64_t seed, uint64_t step, T *wl)
+{
+    NoiseKey nk;
+    nk.k0 = (uint32_t)seed; nk.k1 = (uint32_t)(seed >> 32);
+    nk.s0 = (uint32_t)step; nk.s1 = (uint32_t)(step >> 32);
+    nk.step_dev = nullptr;
+    RsghmcOp<T, POW2, INJECT> op{theta, p, grad, xi, a.rs_eps, a.rs_mass, a.rs_D, a.rs_m2c2, a.rs_nscale, a.grad_decay, nk,
+                                 nullptr, nullptr, a.rs_inv};
+    return run_update_with<TABLE>(op, srow, a.n_params, wl);
+}
+
+// KIND_: the update operator (0 SGHMC, 1 SGLD, 2 relativistic SGHMC), + FUSED_TABLE when the operator's scalars come from
+// FusedArgs::scalars_steps (row t at step t: a stepsize schedule inside the launch) instead of by value. A template
+// parameter, not a branch: bnn_fused_sghmc_kernel<T, 0> and <T, 1> are the by-value kernels they always were.
+template <typename T, int KIND_>
 __global__ void __launch_bounds__(FUSED_THREADS) bnn_fused_sghmc_kernel(const FusedArgs<T> a)
 {
+    constexpr int KIND = KIND_ & 3;
+    constexpr bool TABLE = (KIND_ & FUSED_TABLE) != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     double *red = reinterpret_cast<double *>(smem_raw);           // 17 doubles (+ pad to 160 B)
     T *lds = reinterpret_cast<T *>(smem_raw + 160);
     const int chain = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const size_t cs = (size_t)chain * a.chain_stride;
-    T *theta = a.theta + cs, *V = KIND == 0 ? a.V + cs : nullptr, *grad = a.grad + cs;
-    T *tau = a.tau + cs, *g = a.g + cs, *vh = a.vh + cs, *minv = a.minv + cs;
+    T *theta = a.theta + cs, *V = KIND != 1 ? a.V + cs : nullptr, *grad = a.grad + cs;
+    T *tau = KIND != 2 ? a.tau + cs : nullptr, *g = KIND != 2 ? a.g + cs : nullptr;
+    T *vh = KIND != 2 ? a.vh + cs : nullptr, *minv = KIND != 2 ? a.minv + cs : nullptr;
     const int L = a.n_layers, B = a.batch;
     const uint64_t seed = a.seed_base + (uint64_t)chain;
     T *yb = lds + a.lds_y;
@@ -336,55 +378,85 @@ __global__ void __launch_bounds__(FUSED_THREADS) bnn_fused_sghmc_kernel(const Fu
             }
             __syncthreads();
         }
-        // ---- fused update (K1's or K2's operator) + sum(theta'^2)
+        // ---- fused update (K1's, K2's or K3's operator) + sum(theta'^2)
         const bool adapt = step < a.burn_in_steps || a.burn_in_steps == 0;
         const T *xi = (a.xi != nullptr && chain == 0) ? a.xi + (size_t)t * a.n_params : nullptr;
+        const T *srow = TABLE ? a.scalars_steps + 5 * t : nullptr;
         double share;
-        if (adapt) {
-            share = xi ? update_phase<T, KIND, true, true>(a, theta, V, grad, tau, g, vh, minv, xi, seed, step, wl)
-                       : update_phase<T, KIND, true, false>(a, theta, V, grad, tau, g, vh, minv, xi, seed, step, wl);
+        if constexpr (KIND == 2) {
+            if (!TABLE && a.rs_pow2) {
+                share = xi ? update_phase_rsghmc<T, TABLE, true, true>(a, theta, V, grad, xi, srow, seed, step, wl)
+                           : update_phase_rsghmc<T, TABLE, true, false>(a, theta, V, grad, xi, srow, seed, step, wl);
+            } else {
+                share = xi ? update_phase_rsghmc<T, TABLE, false, true>(a, theta, V, grad, xi, srow, seed, step, wl)
+                           : update_phase_rsghmc<T, TABLE, false, false>(a, theta, V, grad, xi, srow, seed, step, wl);
+            }
+        } else if (adapt) {
+            share = xi ? update_phase<T, KIND, TABLE, true, true>(a, theta, V, grad, tau, g, vh, minv, xi, srow, seed, step, wl)
+                       : update_phase<T, KIND, TABLE, true, false>(a, theta, V, grad, tau, g, vh, minv, xi, srow, seed, step, wl);
         } else {
-            share = xi ? update_phase<T, KIND, false, true>(a, theta, V, grad, tau, g, vh, minv, xi, seed, step, wl)
-                       : update_phase<T, KIND, false, false>(a, theta, V, grad, tau, g, vh, minv, xi, seed, step, wl);
+            share = xi ? update_phase<T, KIND, TABLE, false, true>(a, theta, V, grad, tau, g, vh, minv, xi, srow, seed, step, wl)
+                       : update_phase<T, KIND, TABLE, false, false>(a, theta, V, grad, tau, g, vh, minv, xi, srow, seed, step, wl);
         }
         __threadfence_block();
         tsq = block_sum(share, red);                      // barriers inside: the new theta is visible to the block
     }
 }
 
+template <typename T, int KIND, bool TABLE>
+int launch_fused(const FusedArgs<T> &a, int n_chains, size_t lds_bytes, hipStream_t st)
+{
+    auto kernel = &bnn_fused_sghmc_kernel<T, KIND | (TABLE ? FUSED_TABLE : 0)>;
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)lds_bytes);
+        if (e0 != hipSuccess) return hip_fail(e0, "hipFuncSetAttribute(bnn_fused_sghmc_kernel)");
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_chains), dim3(FUSED_THREADS), lds_bytes, st, a);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "launch bnn_fused_sghmc_kernel");
+}
+
+// `mom`: V (KIND 0), unused (KIND 1), p (KIND 2). `sc`: HOST block of the operator's five by-value scalars (sgmcmc_scalars.hpp).
+// `scalars_steps`: DEVICE table [n_steps][5] that replaces them step by step, or NULL; `need_table`: the entry point has no
+// by-value stepsize, so NULL is an error.
 template <typename T, int KIND>
-int bnn_fused_steps(T *theta, T *V, T *grad, T *tau, T *g, T *v_hat, T *minv, size_t n_params, size_t chain_stride,
-                    int n_chains, const int *layer_sizes, int n_layers, const T *X, const T *y, size_t n_data,
-                    const int *window_starts, int batch, double batch_size, double n_examples, double wdecay,
-                    double prior_mean, double prior_var, T eps, T scale_grad, T mdecay /* SGLD: A */, uint64_t first_step,
-                    uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base, const T *xi, T *cost_out, hipStream_t st)
+int bnn_fused_steps(const char *what, T *theta, T *mom, T *grad, T *tau, T *g, T *v_hat, T *minv, size_t n_params,
+                    size_t chain_stride, int n_chains, const int *layer_sizes, int n_layers, const T *X, const T *y,
+                    size_t n_data, const int *window_starts, int batch, double batch_size, double n_examples, double wdecay,
+                    double prior_mean, double prior_var, const T (&sc)[5], const T *scalars_steps, bool need_table,
+                    uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base, const T *xi, T *cost_out,
+                    hipStream_t st)
 {
     if (n_steps == 0 || n_chains == 0) return 0;
-    if (!theta || (KIND == 0 && !V) || !grad || !tau || !g || !v_hat || !minv || !layer_sizes || !X || !y || !window_starts ||
-        !cost_out)
-        return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: NULL argument");
-    if (n_layers < 1 || n_layers > FUSED_MAX_LAYERS) return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: 1..8 layers");
-    if (layer_sizes[n_layers] != 1) return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: the last layer must have one unit");
-    if (batch < 1 || (size_t)batch > n_data) return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: bad batch");
-    if (xi && (n_params % 4) != 0) return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: injected xi needs n_params %% 4 == 0");
+    const bool stats_rows = KIND != 2;                    // tau, g, v_hat, minv: the burn-in samplers' preconditioner state
+    if (!theta || (KIND != 1 && !mom) || !grad || (stats_rows && (!tau || !g || !v_hat || !minv)) || !layer_sizes || !X || !y ||
+        !window_starts || !cost_out)
+        return fail(SGMCMC_EINVAL, "%s: NULL argument", what);
+    if (need_table && !scalars_steps) return fail(SGMCMC_EINVAL, "%s: scalars_steps is NULL", what);
+    if (n_layers < 1 || n_layers > FUSED_MAX_LAYERS) return fail(SGMCMC_EINVAL, "%s: 1..8 layers", what);
+    if (layer_sizes[n_layers] != 1) return fail(SGMCMC_EINVAL, "%s: the last layer must have one unit", what);
+    if (batch < 1 || (size_t)batch > n_data) return fail(SGMCMC_EINVAL, "%s: bad batch", what);
+    if (xi && (n_params % 4) != 0) return fail(SGMCMC_EINVAL, "%s: injected xi needs n_params %% 4 == 0", what);
     if (n_chains > 1 && (chain_stride < n_params || (chain_stride % 4) != 0))
-        return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: chain_stride must be >= n_params and a multiple of 4");
-    T *rows[7] = {theta, KIND == 0 ? V : theta, grad, tau, g, v_hat, minv};
+        return fail(SGMCMC_EINVAL, "%s: chain_stride must be >= n_params and a multiple of 4", what);
+    T *rows[7] = {theta, KIND != 1 ? mom : theta, grad, stats_rows ? tau : theta, stats_rows ? g : theta,
+                  stats_rows ? v_hat : theta, stats_rows ? minv : theta};
     for (T *p : rows)
-        if (reinterpret_cast<uintptr_t>(p) & 15u) return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: rows must be 16-B aligned");
-    FusedArgs<T> a;
-    a.theta = theta; a.V = V; a.grad = grad; a.tau = tau; a.g = g; a.vh = v_hat; a.minv = minv;
+        if (reinterpret_cast<uintptr_t>(p) & 15u) return fail(SGMCMC_EINVAL, "%s: rows must be 16-B aligned", what);
+    FusedArgs<T> a{};
+    a.theta = theta; a.V = mom; a.grad = grad; a.tau = tau; a.g = g; a.vh = v_hat; a.minv = minv;
     a.n_params = n_params; a.chain_stride = chain_stride; a.n_layers = n_layers;
     size_t off = 0, lds_elems = 0;
     for (int l = 0; l <= n_layers; ++l) {
-        if (layer_sizes[l] < 1) return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: bad layer size");
+        if (layer_sizes[l] < 1) return fail(SGMCMC_EINVAL, "%s: bad layer size", what);
         a.sizes[l] = layer_sizes[l];
     }
     for (int l = 1; l <= n_layers; ++l) {                  // parameter order: W1, b1, ..., WL, bL, log_var
         a.off_w[l] = off; off += (size_t)a.sizes[l - 1] * a.sizes[l];
         a.off_b[l] = off; off += (size_t)a.sizes[l];
     }
-    if (off + 1 != n_params) return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: n_params does not match the layer sizes");
+    if (off + 1 != n_params) return fail(SGMCMC_EINVAL, "%s: n_params does not match the layer sizes", what);
     for (int l = 0; l <= n_layers; ++l) { a.act_off[l] = lds_elems; lds_elems += (size_t)batch * a.sizes[l]; }
     a.del_off[0] = 0;
     for (int l = 1; l <= n_layers; ++l) { a.del_off[l] = lds_elems; lds_elems += (size_t)batch * a.sizes[l]; }
@@ -392,100 +464,216 @@ int bnn_fused_steps(T *theta, T *V, T *grad, T *tau, T *g, T *v_hat, T *minv, si
     lds_elems = (lds_elems + 3) & ~(size_t)3;
     a.lds_w = lds_elems; lds_elems += n_params;
     const size_t lds_bytes = 160 + lds_elems * sizeof(T);
-    if (lds_bytes > 160 * 1024) return fail(SGMCMC_EINVAL, "bnn_fused_sghmc_steps: activations need %zu B of LDS (> 160 KiB); "
-                                            "use the GEMM path", lds_bytes);
+    if (lds_bytes > 160 * 1024) return fail(SGMCMC_EINVAL, "%s: activations need %zu B of LDS (> 160 KiB); "
+                                            "use the GEMM path", what, lds_bytes);
     a.X = X; a.y = y; a.n_data = n_data; a.starts = window_starts; a.batch = batch;
     a.batch_size = batch_size; a.n_examples = n_examples; a.wdecay = wdecay;
     a.wp_den = (double)n_params + (2.0 * 1e-16 + 1e-16);
     a.lvp_den = 2.0 * prior_var + (2.0 * 1e-16 + 1e-16);
     a.ln_prior_mean = std::log(prior_mean); a.ln_prior_var = std::log(prior_var);
-    // K1's host-derived scalars (sghmc.py:111-117,211-217,235), same op order
-    T eps_s = eps / std::sqrt(scale_grad);
-    a.eps_e2 = std::pow(eps, T(2));
-    a.c1 = (T(2) * std::pow(eps_s, T(2))) * mdecay;
-    a.c3 = T(2) * std::pow(eps_s, T(3));
-    a.e4 = std::pow(eps_s, T(4));
-    a.mdecay = mdecay;
-    // K2's host-derived scalars (sgld.py:106-108,186-191), same op order as sgld_step in sgmcmc_kernels.hip
-    {
-        const T A = mdecay;                               // the SGLD entry passes A in this slot
-        const T sgn = (scale_grad > T(0)) ? T(1) : ((scale_grad < T(0)) ? T(-1) : T(0));
-        a.sgld_den = scale_grad + ((T(2) * sgn) * T(1e-16) + T(1e-16));
-        a.sgld_two_eps = T(2) * eps;
-        a.sgld_a_eff = A - T(0);
-        a.sgld_eps = eps;
-        a.sgld_A = A;
+    if (KIND == 0) { a.eps_e2 = sc[0]; a.c1 = sc[1]; a.c3 = sc[2]; a.e4 = sc[3]; a.mdecay = sc[4]; }
+    if (KIND == 1) { a.sgld_eps = sc[0]; a.sgld_A = sc[1]; a.sgld_a_eff = sc[2]; a.sgld_two_eps = sc[3]; a.sgld_den = sc[4]; }
+    if (KIND == 2) {
+        a.rs_eps = sc[0]; a.rs_mass = sc[1]; a.rs_D = sc[2]; a.rs_m2c2 = sc[3]; a.rs_nscale = sc[4];
+        // POW2 as in sgmcmc_rsghmc.hip; not with a table, whose rows carry their own m2c2
+        a.rs_pow2 = (rsghmc_m2c2_is_pow2<T>(sc[3], a.rs_inv) && !scalars_steps) ? 1 : 0;
     }
     a.grad_decay = (T)(wdecay / (a.wp_den * n_examples));   // weight-prior gradient, folded into the update
     a.first_step = first_step; a.n_steps = n_steps; a.burn_in_steps = burn_in_steps; a.seed_base = seed_base;
-    a.xi = xi; a.cost_out = cost_out;
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&bnn_fused_sghmc_kernel<T, KIND>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e0 != hipSuccess) return hip_fail(e0, "hipFuncSetAttribute(bnn_fused_sghmc_kernel)");
+    a.xi = xi; a.cost_out = cost_out; a.scalars_steps = scalars_steps;
+    return scalars_steps ? launch_fused<T, KIND, true>(a, n_chains, lds_bytes, st)
+                         : launch_fused<T, KIND, false>(a, n_chains, lds_bytes, st);
+}
+
+// the existing by-value entry points and their table twins: SGHMC (eps, scale_grad, mdecay), SGLD (eps, scale_grad, A)
+template <typename T, int KIND>
+int bnn_fused_burn_in_steps(const char *what, T *theta, T *V, T *grad, T *tau, T *g, T *v_hat, T *minv, size_t n_params,
+                            size_t chain_stride, int n_chains, const int *layer_sizes, int n_layers, const T *X, const T *y,
+                            size_t n_data, const int *window_starts, int batch, double batch_size, double n_examples,
+                            double wdecay, double prior_mean, double prior_var, T eps, T scale_grad, T mdecay_or_A,
+                            const T *scalars_steps, bool need_table, uint64_t first_step, uint64_t n_steps,
+                            uint64_t burn_in_steps, uint64_t seed_base, const T *xi, T *cost_out, sgmcmc_stream_t stream)
+{
+    T sc[5] = {T(0), T(0), T(0), T(0), T(0)};
+    if (!need_table) {
+        if (KIND == 0) sghmc_scalars<T>(eps, scale_grad, mdecay_or_A, sc);
+        else sgld_scalars<T>(eps, mdecay_or_A, scale_grad, sc);
     }
-    hipLaunchKernelGGL((bnn_fused_sghmc_kernel<T, KIND>), dim3((unsigned)n_chains), dim3(FUSED_THREADS), lds_bytes, st, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "launch bnn_fused_sghmc_kernel");
+    return bnn_fused_steps<T, KIND>(what, theta, V, grad, tau, g, v_hat, minv, n_params, chain_stride, n_chains, layer_sizes,
+                                    n_layers, X, y, n_data, window_starts, batch, batch_size, n_examples, wdecay, prior_mean,
+                                    prior_var, sc, scalars_steps, need_table, first_step, n_steps, burn_in_steps, seed_base, xi,
+                                    cost_out, static_cast<hipStream_t>(stream));
+}
+
+template <typename T>
+int bnn_fused_rsghmc(T *theta, T *p, T *grad, size_t n_params, size_t chain_stride, int n_chains, const int *layer_sizes,
+                     int n_layers, const T *X, const T *y, size_t n_data, const int *window_starts, int batch,
+                     double batch_size, double n_examples, double wdecay, double prior_mean, double prior_var, T eps, T mass,
+                     T c, T D, T b_hat, const T *scalars_steps, uint64_t first_step, uint64_t n_steps, uint64_t seed_base,
+                     const T *xi, T *cost_out, sgmcmc_stream_t stream)
+{
+    T sc[5];
+    rsghmc_scalars<T>(eps, mass, c, D, b_hat, sc);
+    return bnn_fused_steps<T, 2>("bnn_fused_rsghmc_steps", theta, p, grad, nullptr, nullptr, nullptr, nullptr, n_params,
+                                 chain_stride, n_chains, layer_sizes, n_layers, X, y, n_data, window_starts, batch, batch_size,
+                                 n_examples, wdecay, prior_mean, prior_var, sc, scalars_steps, false, first_step, n_steps, 0,
+                                 seed_base, xi, cost_out, static_cast<hipStream_t>(stream));
+}
+
+// HOST table [n_steps][5] of an operator's scalars for the stepsizes eps[0 .. n_steps): `derive(eps, row)` is the shared derivation
+template <typename T, typename F>
+int scalars_steps_fill(const char *what, const T *eps, size_t n_steps, T *block, F derive)
+{
+    if (n_steps == 0) return 0;
+    if (!eps || !block) return fail(SGMCMC_EINVAL, "%s: eps_host and block_host must be non-NULL", what);
+    for (size_t t = 0; t < n_steps; ++t) {
+        T s[5];
+        derive(eps[t], s);
+        for (int k = 0; k < 5; ++k) block[5 * t + k] = s[k];
+    }
+    return 0;
 }
 
 }  // namespace
 
+#define FUSED_COMMON_PARAMS(T)                                                                                             \
+    size_t n_params, size_t chain_stride, int n_chains, const int *layer_sizes, int n_layers, const T *X, const T *y,      \
+    size_t n_data, const int *window_starts, int batch, double batch_size, double n_examples, double wdecay,               \
+    double prior_mean, double prior_var
+#define FUSED_COMMON_ARGS                                                                                                   \
+    n_params, chain_stride, n_chains, layer_sizes, n_layers, X, y, n_data, window_starts, batch, batch_size, n_examples,    \
+    wdecay, prior_mean, prior_var
+
 extern "C" {
 
 int sgmcmc_bnn_fused_sghmc_steps_f32(float *theta, float *V, float *grad, float *tau, float *g, float *v_hat, float *minv,
-                                     size_t n_params, size_t chain_stride, int n_chains, const int *layer_sizes,
-                                     int n_layers, const float *X, const float *y, size_t n_data,
-                                     const int *window_starts, int batch, double batch_size, double n_examples,
-                                     double wdecay, double prior_mean, double prior_var, float eps, float scale_grad,
-                                     float mdecay, uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps,
-                                     uint64_t seed_base, const float *xi, float *cost_out, sgmcmc_stream_t stream)
+                                     FUSED_COMMON_PARAMS(float), float eps, float scale_grad, float mdecay,
+                                     uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base,
+                                     const float *xi, float *cost_out, sgmcmc_stream_t stream)
 {
-    return bnn_fused_steps<float, 0>(theta, V, grad, tau, g, v_hat, minv, n_params, chain_stride, n_chains, layer_sizes,
-                                  n_layers, X, y, n_data, window_starts, batch, batch_size, n_examples, wdecay,
-                                  prior_mean, prior_var, eps, scale_grad, mdecay, first_step, n_steps, burn_in_steps,
-                                  seed_base, xi, cost_out, static_cast<hipStream_t>(stream));
+    return bnn_fused_burn_in_steps<float, 0>("bnn_fused_sghmc_steps", theta, V, grad, tau, g, v_hat, minv, FUSED_COMMON_ARGS,
+                                             eps, scale_grad, mdecay, nullptr, false, first_step, n_steps, burn_in_steps,
+                                             seed_base, xi, cost_out, stream);
 }
 int sgmcmc_bnn_fused_sghmc_steps_f64(double *theta, double *V, double *grad, double *tau, double *g, double *v_hat,
-                                     double *minv, size_t n_params, size_t chain_stride, int n_chains,
-                                     const int *layer_sizes, int n_layers, const double *X, const double *y,
-                                     size_t n_data, const int *window_starts, int batch, double batch_size,
-                                     double n_examples, double wdecay, double prior_mean, double prior_var, double eps,
-                                     double scale_grad, double mdecay, uint64_t first_step, uint64_t n_steps,
-                                     uint64_t burn_in_steps, uint64_t seed_base, const double *xi, double *cost_out,
-                                     sgmcmc_stream_t stream)
+                                     double *minv, FUSED_COMMON_PARAMS(double), double eps, double scale_grad, double mdecay,
+                                     uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base,
+                                     const double *xi, double *cost_out, sgmcmc_stream_t stream)
 {
-    return bnn_fused_steps<double, 0>(theta, V, grad, tau, g, v_hat, minv, n_params, chain_stride, n_chains, layer_sizes,
-                                   n_layers, X, y, n_data, window_starts, batch, batch_size, n_examples, wdecay,
-                                   prior_mean, prior_var, eps, scale_grad, mdecay, first_step, n_steps, burn_in_steps,
-                                   seed_base, xi, cost_out, static_cast<hipStream_t>(stream));
+    return bnn_fused_burn_in_steps<double, 0>("bnn_fused_sghmc_steps", theta, V, grad, tau, g, v_hat, minv, FUSED_COMMON_ARGS,
+                                              eps, scale_grad, mdecay, nullptr, false, first_step, n_steps, burn_in_steps,
+                                              seed_base, xi, cost_out, stream);
 }
-
 int sgmcmc_bnn_fused_sgld_steps_f32(float *theta, float *grad, float *tau, float *g, float *v_hat, float *minv,
-                                    size_t n_params, size_t chain_stride, int n_chains, const int *layer_sizes,
-                                    int n_layers, const float *X, const float *y, size_t n_data,
-                                    const int *window_starts, int batch, double batch_size, double n_examples,
-                                    double wdecay, double prior_mean, double prior_var, float eps, float scale_grad,
-                                    float A, uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps,
-                                    uint64_t seed_base, const float *xi, float *cost_out, sgmcmc_stream_t stream)
+                                    FUSED_COMMON_PARAMS(float), float eps, float scale_grad, float A, uint64_t first_step,
+                                    uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base, const float *xi,
+                                    float *cost_out, sgmcmc_stream_t stream)
 {
-    return bnn_fused_steps<float, 1>(theta, nullptr, grad, tau, g, v_hat, minv, n_params, chain_stride, n_chains,
-                                     layer_sizes, n_layers, X, y, n_data, window_starts, batch, batch_size, n_examples,
-                                     wdecay, prior_mean, prior_var, eps, scale_grad, A, first_step, n_steps, burn_in_steps,
-                                     seed_base, xi, cost_out, static_cast<hipStream_t>(stream));
+    return bnn_fused_burn_in_steps<float, 1>("bnn_fused_sghmc_steps", theta, nullptr, grad, tau, g, v_hat, minv,
+                                             FUSED_COMMON_ARGS, eps, scale_grad, A, nullptr, false, first_step, n_steps,
+                                             burn_in_steps, seed_base, xi, cost_out, stream);
 }
 int sgmcmc_bnn_fused_sgld_steps_f64(double *theta, double *grad, double *tau, double *g, double *v_hat, double *minv,
-                                    size_t n_params, size_t chain_stride, int n_chains, const int *layer_sizes,
-                                    int n_layers, const double *X, const double *y, size_t n_data,
-                                    const int *window_starts, int batch, double batch_size, double n_examples,
-                                    double wdecay, double prior_mean, double prior_var, double eps, double scale_grad,
-                                    double A, uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps,
-                                    uint64_t seed_base, const double *xi, double *cost_out, sgmcmc_stream_t stream)
+                                    FUSED_COMMON_PARAMS(double), double eps, double scale_grad, double A, uint64_t first_step,
+                                    uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base, const double *xi,
+                                    double *cost_out, sgmcmc_stream_t stream)
 {
-    return bnn_fused_steps<double, 1>(theta, nullptr, grad, tau, g, v_hat, minv, n_params, chain_stride, n_chains,
-                                      layer_sizes, n_layers, X, y, n_data, window_starts, batch, batch_size, n_examples,
-                                      wdecay, prior_mean, prior_var, eps, scale_grad, A, first_step, n_steps,
-                                      burn_in_steps, seed_base, xi, cost_out, static_cast<hipStream_t>(stream));
+    return bnn_fused_burn_in_steps<double, 1>("bnn_fused_sghmc_steps", theta, nullptr, grad, tau, g, v_hat, minv,
+                                              FUSED_COMMON_ARGS, eps, scale_grad, A, nullptr, false, first_step, n_steps,
+                                              burn_in_steps, seed_base, xi, cost_out, stream);
+}
+
+// ---- include/sgmcmc_hip_fused.h
+
+int sgmcmc_fused_abi_version(void) { return SGMCMC_FUSED_ABI_VERSION; }
+
+int sgmcmc_sghmc_scalars_steps_f32(const float *eps_host, size_t n_steps, float scale_grad, float mdecay, float *block_host)
+{
+    return scalars_steps_fill<float>("sghmc_scalars_steps", eps_host, n_steps, block_host,
+                                     [=](float e, float (&s)[5]) { sghmc_scalars<float>(e, scale_grad, mdecay, s); });
+}
+int sgmcmc_sghmc_scalars_steps_f64(const double *eps_host, size_t n_steps, double scale_grad, double mdecay, double *block_host)
+{
+    return scalars_steps_fill<double>("sghmc_scalars_steps", eps_host, n_steps, block_host,
+                                      [=](double e, double (&s)[5]) { sghmc_scalars<double>(e, scale_grad, mdecay, s); });
+}
+int sgmcmc_sgld_scalars_steps_f32(const float *eps_host, size_t n_steps, float A, float scale_grad, float *block_host)
+{
+    return scalars_steps_fill<float>("sgld_scalars_steps", eps_host, n_steps, block_host,
+                                     [=](float e, float (&s)[5]) { sgld_scalars<float>(e, A, scale_grad, s); });
+}
+int sgmcmc_sgld_scalars_steps_f64(const double *eps_host, size_t n_steps, double A, double scale_grad, double *block_host)
+{
+    return scalars_steps_fill<double>("sgld_scalars_steps", eps_host, n_steps, block_host,
+                                      [=](double e, double (&s)[5]) { sgld_scalars<double>(e, A, scale_grad, s); });
+}
+int sgmcmc_rsghmc_scalars_steps_f32(const float *eps_host, size_t n_steps, float mass, float c, float D, float b_hat,
+                                    float *block_host)
+{
+    return scalars_steps_fill<float>("rsghmc_scalars_steps", eps_host, n_steps, block_host,
+                                     [=](float e, float (&s)[5]) { rsghmc_scalars<float>(e, mass, c, D, b_hat, s); });
+}
+int sgmcmc_rsghmc_scalars_steps_f64(const double *eps_host, size_t n_steps, double mass, double c, double D, double b_hat,
+                                    double *block_host)
+{
+    return scalars_steps_fill<double>("rsghmc_scalars_steps", eps_host, n_steps, block_host,
+                                      [=](double e, double (&s)[5]) { rsghmc_scalars<double>(e, mass, c, D, b_hat, s); });
+}
+
+int sgmcmc_bnn_fused_sghmc_sched_steps_f32(float *theta, float *V, float *grad, float *tau, float *g, float *v_hat,
+                                           float *minv, FUSED_COMMON_PARAMS(float), const float *scalars_steps,
+                                           float scale_grad, float mdecay, uint64_t first_step, uint64_t n_steps,
+                                           uint64_t burn_in_steps, uint64_t seed_base, const float *xi, float *cost_out,
+                                           sgmcmc_stream_t stream)
+{
+    return bnn_fused_burn_in_steps<float, 0>("bnn_fused_sghmc_sched_steps", theta, V, grad, tau, g, v_hat, minv,
+                                             FUSED_COMMON_ARGS, 0.0f, scale_grad, mdecay, scalars_steps, true, first_step,
+                                             n_steps, burn_in_steps, seed_base, xi, cost_out, stream);
+}
+int sgmcmc_bnn_fused_sghmc_sched_steps_f64(double *theta, double *V, double *grad, double *tau, double *g, double *v_hat,
+                                           double *minv, FUSED_COMMON_PARAMS(double), const double *scalars_steps,
+                                           double scale_grad, double mdecay, uint64_t first_step, uint64_t n_steps,
+                                           uint64_t burn_in_steps, uint64_t seed_base, const double *xi, double *cost_out,
+                                           sgmcmc_stream_t stream)
+{
+    return bnn_fused_burn_in_steps<double, 0>("bnn_fused_sghmc_sched_steps", theta, V, grad, tau, g, v_hat, minv,
+                                              FUSED_COMMON_ARGS, 0.0, scale_grad, mdecay, scalars_steps, true, first_step,
+                                              n_steps, burn_in_steps, seed_base, xi, cost_out, stream);
+}
+int sgmcmc_bnn_fused_sgld_sched_steps_f32(float *theta, float *grad, float *tau, float *g, float *v_hat, float *minv,
+                                          FUSED_COMMON_PARAMS(float), const float *scalars_steps, float scale_grad, float A,
+                                          uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base,
+                                          const float *xi, float *cost_out, sgmcmc_stream_t stream)
+{
+    return bnn_fused_burn_in_steps<float, 1>("bnn_fused_sgld_sched_steps", theta, nullptr, grad, tau, g, v_hat, minv,
+                                             FUSED_COMMON_ARGS, 0.0f, scale_grad, A, scalars_steps, true, first_step, n_steps,
+                                             burn_in_steps, seed_base, xi, cost_out, stream);
+}
+int sgmcmc_bnn_fused_sgld_sched_steps_f64(double *theta, double *grad, double *tau, double *g, double *v_hat, double *minv,
+                                          FUSED_COMMON_PARAMS(double), const double *scalars_steps, double scale_grad,
+                                          double A, uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps,
+                                          uint64_t seed_base, const double *xi, double *cost_out, sgmcmc_stream_t stream)
+{
+    return bnn_fused_burn_in_steps<double, 1>("bnn_fused_sgld_sched_steps", theta, nullptr, grad, tau, g, v_hat, minv,
+                                              FUSED_COMMON_ARGS, 0.0, scale_grad, A, scalars_steps, true, first_step, n_steps,
+                                              burn_in_steps, seed_base, xi, cost_out, stream);
+}
+
+int sgmcmc_bnn_fused_rsghmc_steps_f32(float *theta, float *p, float *grad, FUSED_COMMON_PARAMS(float), float eps, float mass,
+                                      float c, float D, float b_hat, const float *scalars_steps, uint64_t first_step,
+                                      uint64_t n_steps, uint64_t seed_base, const float *xi, float *cost_out,
+                                      sgmcmc_stream_t stream)
+{
+    return bnn_fused_rsghmc<float>(theta, p, grad, FUSED_COMMON_ARGS, eps, mass, c, D, b_hat, scalars_steps, first_step,
+                                   n_steps, seed_base, xi, cost_out, stream);
+}
+int sgmcmc_bnn_fused_rsghmc_steps_f64(double *theta, double *p, double *grad, FUSED_COMMON_PARAMS(double), double eps,
+                                      double mass, double c, double D, double b_hat, const double *scalars_steps,
+                                      uint64_t first_step, uint64_t n_steps, uint64_t seed_base, const double *xi,
+                                      double *cost_out, sgmcmc_stream_t stream)
+{
+    return bnn_fused_rsghmc<double>(theta, p, grad, FUSED_COMMON_ARGS, eps, mass, c, D, b_hat, scalars_steps, first_step,
+                                    n_steps, seed_base, xi, cost_out, stream);
 }
 
 }  // extern "C"

@@ -2,20 +2,10 @@
 // side of sgmcmc_rsghmc_step_{f32,f64} and sgmcmc_rsghmc_scalars_*. Arithmetic: RsghmcOp (sgmcmc_device.hpp).
 #include <cmath>
 
+#include "sgmcmc_scalars.hpp"
 #include "sgmcmc_stream.hpp"
 
 namespace {
-
-// {eps, mass, D, m2c2, nscale}, relativistic_sghmc.py:105-106,117-125
-template <typename T>
-void rsghmc_scalars(T eps, T mass, T c, T D, T b_hat, T (&s)[5])
-{
-    s[0] = eps;
-    s[1] = mass;
-    s[2] = D;
-    s[3] = (mass * mass) * (c * c);
-    s[4] = std::sqrt(eps * ((T(2) * D) - (eps * b_hat)));
-}
 
 template <typename T>
 int rsghmc_step(T *theta, T *p, const T *grad, size_t n, T eps, T mass, T c, T D, T b_hat, T grad_decay,
@@ -39,10 +29,8 @@ int rsghmc_step(T *theta, T *p, const T *grad, size_t n, T eps, T mass, T c, T D
     int rc;
     // m^2 c^2 a power of two (the default m = c = 1): the divisions by it are exact multiplications (RsghmcOp POW2). Not with
     // device-resident scalars: the block may be refreshed with another mass / c after this launch was captured.
-    int e2 = 0;
-    const T inv = T(1) / s[3];
-    const bool pow2 = sdev == nullptr && s[3] > T(0) && std::isfinite(s[3]) && std::frexp(s[3], &e2) == T(0.5) &&
-                      std::isnormal(inv) && std::isnormal(s[3]);
+    T inv;
+    const bool pow2 = rsghmc_m2c2_is_pow2<T>(s[3], inv) && sdev == nullptr;
 #define RSGHMC_GO(P2, INJ)                                                                                        \
     {                                                                                                             \
         RsghmcOp<T, P2, INJ> op{theta, p, grad, xi, s[0], s[1], s[2], s[3], s[4], grad_decay, nk, sp, sdev, inv};  \

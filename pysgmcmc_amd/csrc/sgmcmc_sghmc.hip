@@ -3,21 +3,10 @@
 // The arithmetic is SghmcOp (sgmcmc_device.hpp), the kernel shape stream_quads_vec (sgmcmc_stream.hpp).
 #include <cmath>
 
+#include "sgmcmc_scalars.hpp"
 #include "sgmcmc_stream.hpp"
 
 namespace {
-
-// scalars of the reference graph, in the dtype, same op order (sghmc.py:111-117,211-217,235): {e2, c1, c3, e4, mdecay}
-template <typename T>
-void sghmc_scalars(T eps, T scale_grad, T mdecay, T (&s)[5])
-{
-    T eps_s = eps / std::sqrt(scale_grad);
-    s[0] = std::pow(eps, T(2));
-    s[1] = (T(2) * std::pow(eps_s, T(2))) * mdecay;
-    s[2] = T(2) * std::pow(eps_s, T(3));
-    s[3] = std::pow(eps_s, T(4));
-    s[4] = mdecay;
-}
 
 template <typename T>
 int sghmc_step(T *theta, T *V, const T *grad, T *tau, T *g, T *v_hat, T *minv, T *r, size_t n,

@@ -2,21 +2,10 @@
 // sgmcmc_sgld_step_{f32,f64} and sgmcmc_sgld_scalars_*. Arithmetic: SgldOp (sgmcmc_device.hpp).
 #include <cmath>
 
+#include "sgmcmc_scalars.hpp"
 #include "sgmcmc_stream.hpp"
 
 namespace {
-
-// {eps, A, a_eff, two_eps, sg_den}, sgld.py:106-108,186-191,201-204
-template <typename T>
-void sgld_scalars(T eps, T A, T scale_grad, T (&s)[5])
-{
-    T sgn = (scale_grad > T(0)) ? T(1) : ((scale_grad < T(0)) ? T(-1) : T(0));
-    s[0] = eps;
-    s[1] = A;
-    s[2] = A - T(0);
-    s[3] = T(2) * eps;
-    s[4] = scale_grad + ((T(2) * sgn) * T(1e-16) + T(1e-16));
-}
 
 template <typename T>
 int sgld_step(T *theta, const T *grad, T *tau, T *g, T *v_hat, T *minv, T *r, size_t n,

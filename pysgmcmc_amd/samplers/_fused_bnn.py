@@ -1,5 +1,8 @@
-"""Whole steps of a small BNN in one kernel (csrc/sgmcmc_bnn_fused.hip), shared by the two samplers the
-reference's BNN accepts (``pysgmcmc/sampling.py:40,64``: SGHMC and SGLD)."""
+"""Whole steps of a small BNN in one kernel (csrc/sgmcmc_bnn_fused.hip), shared by the samplers of the hot path:
+SGHMC and SGLD (the two the reference's BNN accepts, ``pysgmcmc/sampling.py:40,64``) and relativistic SGHMC.
+
+The stepsize may move inside a chunk: the kernel then reads each step's derived scalars from a device table built on the
+host from the schedule's values (``kernels.step_scalars_table``); a chunk at one stepsize is launched by value."""
 import numpy as np
 import torch
 
@@ -9,11 +12,11 @@ __all__ = ("FusedBNNStepsMixin",)
 
 
 class FusedBNNStepsMixin(object):
-    """``fused_bnn_available()`` / ``fused_bnn_steps(n)`` for burn-in samplers; the sampler supplies
-    ``_fused_bnn_launch(starts, costs, eps, n_steps)``."""
+    """``fused_bnn_available()`` / ``fused_bnn_steps(n)``; the sampler supplies ``_FUSED_ROWS``, ``_SCALARS_KIND`` /
+    ``_step_scalars(eps)`` and ``_fused_bnn_launch(starts, costs, eps, n_steps, ..., scalars_steps=None)``."""
 
     def fused_bnn_available(self):
-        """True when whole steps can run inside ONE kernel (``sgmcmc_bnn_fused_{sghmc,sgld}_steps``): the cost is
+        """True when whole steps can run inside ONE kernel (``sgmcmc_bnn_fused_{sghmc,sgld,rsghmc}_steps``): the cost is
         the library's MLP-BNN cost (``BNNCost``, weight prior folded), fed by a ``WindowBatches`` generator,
         the net has one output unit, at most 8 layers, and its activations fit the LDS."""
         cost, gen = self.cost_fun, self.batch_generator
@@ -41,18 +44,29 @@ class FusedBNNStepsMixin(object):
             sizes.append(w[1])
         return sizes
 
+    def _fused_scalars_table(self, eps):
+        """Device table of the chunk's per-step scalars for the stepsizes ``eps``, or None when they are all equal (the
+        launch then takes ``eps[0]`` by value)."""
+        if all(e == eps[0] for e in eps):
+            return None
+        return kernels.step_scalars_table(self._SCALARS_KIND, eps, *self._step_scalars(eps[0])[1:],
+                                          dtype=self._torch_dtype, device=self.device)
+
     def fused_bnn_steps(self, n_steps):
         """Advance the chain by ``n_steps`` complete steps in one launch (one workgroup; see
         ``csrc/sgmcmc_bnn_fused.hip``). Same chain as ``n_steps`` calls of ``next()`` up to the rounding of
         the matrix products (same windows, same Philox stream, same update operator). Returns the
-        device tensor of the ``n_steps`` costs. Needs a stepsize that is constant over the chunk."""
+        device tensor of the ``n_steps`` costs.
+
+        The ``n_steps`` stepsizes are drawn from the schedule up front; ``epsilon`` ends as the last one. The schedule's
+        ``update(params, cost)`` is not called inside a chunk (nor after it), so a schedule that needs that feedback per
+        step has to be stepped with ``next()``."""
         if not self.fused_bnn_available():
             raise ValueError("fused_bnn_steps: this sampler/cost/batch generator does not fit the fused small-model kernel")
         n_steps = int(n_steps)
         eps = [next(self.stepsize_schedule) for _ in range(n_steps)]
-        if any(e != eps[0] for e in eps):
-            raise ValueError("fused_bnn_steps needs a constant stepsize over the chunk")
-        self.epsilon = eps[0]
+        table = self._fused_scalars_table(eps)
+        self.epsilon = eps[-1]
         gen, cost, a = self.batch_generator, self.cost_fun, self.arena
         pending, self._pending_window = getattr(self, "_pending_window", None), None
         if pending is None:
@@ -62,7 +76,10 @@ class FusedBNNStepsMixin(object):
         starts_host = np.concatenate([np.asarray(first, dtype=np.int32), gen.next_starts(n_steps - len(first))]) if first else gen.next_starts(n_steps)
         starts = torch.as_tensor(starts_host, dtype=torch.int32).to(self.device)
         costs = torch.empty(n_steps, dtype=self._torch_dtype, device=self.device)
-        self._fused_bnn_launch(starts, costs, eps[0], n_steps)
+        if table is None:
+            self._fused_bnn_launch(starts, costs, eps[0], n_steps)
+        else:
+            self._fused_bnn_launch(starts, costs, eps[0], n_steps, scalars_steps=table)
         self.n_iterations += n_steps
         self._stats_valid = False                 # theta moved without the statistics workspace
         self._grad_decay = float(cost.wdecay / ((a.n + 3e-16) * cost.n_examples))

@@ -1,12 +1,15 @@
-"""Many independent SGHMC chains of one small BNN advanced together by the fused-step kernel.
+"""Many independent chains of one small BNN (all SGHMC, all SGLD or all relativistic SGHMC) advanced together by the
+fused-step kernel.
 
 The reference runs chains one after the other, each in a fresh TF graph
 (``pysgmcmc/diagnostics/sample_chains.py:369-382``). ``sgmcmc_bnn_fused_sghmc_steps_*`` runs one
 workgroup per chain, so up to one chain per CU (256 on MI355X) advance in the time of one: the chains'
 states are re-homed back to back in ONE allocation (chain ``c`` at ``+ c * chain_stride`` in every state
-row) and every launch covers ``n_steps`` steps of all of them. Each chain stays a normal
-:class:`~pysgmcmc_amd.samplers.sghmc.SGHMCSampler` (``next()``, ``minv``, ``state_dict`` ... keep working on
-the shared memory); chain ``c`` uses Philox seed ``seed_0 + c`` and its own window stream.
+row) and every launch covers ``n_steps`` steps of all of them. Each chain stays a normal sampler
+(:class:`~pysgmcmc_amd.samplers.sghmc.SGHMCSampler`, ``SGLDSampler`` or ``RelativisticSGHMCSampler``: ``next()``,
+``minv``, ``state_dict`` ... keep working on the shared memory); chain ``c`` uses Philox seed ``seed_0 + c`` and its own
+window stream. The stepsize may follow a schedule as long as every chain's schedule yields the same values: the launch
+then reads ONE table of per-step scalars that all chains share.
 """
 import numpy as np
 import torch
@@ -17,11 +20,11 @@ __all__ = ("FusedBNNChains",)
 
 
 class FusedBNNChains(object):
-    """Group of SGHMC (or of SGLD) chains that fit the fused small-model kernel.
+    """Group of SGHMC (or of SGLD, or of relativistic SGHMC) chains that fit the fused small-model kernel.
 
     Parameters
     ----------
-    samplers : list of SGHMCSampler (or list of SGLDSampler)
+    samplers : list of SGHMCSampler (or list of SGLDSampler, or list of RelativisticSGHMCSampler)
         Chains over the SAME dataset and network shape, built with ``seed = s, s + 1, s + 2, ...``, equal
         hyper-parameters and ``fused_bnn_available()``; all at the same iteration.
     """
@@ -38,10 +41,10 @@ class FusedBNNChains(object):
                     and s.batch_generator.x_dev.data_ptr() == first.batch_generator.x_dev.data_ptr()
                     and s.batch_generator.y_dev.data_ptr() == first.batch_generator.y_dev.data_ptr()
                     and s.batch_generator.batch_size == first.batch_generator.batch_size
-                    and s.n_iterations == first.n_iterations and s.burn_in_steps == first.burn_in_steps
-                    and s.scale_grad == first.scale_grad
-                    and getattr(s, "mdecay", None) == getattr(first, "mdecay", None)
-                    and getattr(s, "A", None) == getattr(first, "A", None)
+                    and s.n_iterations == first.n_iterations
+                    # hyper-parameters: whichever of them the sampler class has
+                    and all(getattr(s, k, None) == getattr(first, k, None)
+                            for k in ("burn_in_steps", "scale_grad", "mdecay", "A", "mass", "speed_of_light", "D", "Bhat"))
                     and all(getattr(s.cost_fun, k) == getattr(first.cost_fun, k)
                             for k in ("batch_size", "n_examples", "wdecay", "prior_mean", "prior_var")))
             if not same:
@@ -68,7 +71,8 @@ class FusedBNNChains(object):
 
     def steps(self, n_steps):
         """Advance every chain by ``n_steps`` steps in one launch; returns the ``[n_chains, n_steps]`` costs
-        (cost at the parameters before each step). Needs a stepsize that is constant over the chunk."""
+        (cost at the parameters before each step). The stepsize may move inside the chunk when every chain's schedule
+        yields the same ``n_steps`` values (one shared table of per-step scalars); chains whose schedules disagree raise."""
         n_steps = int(n_steps)
         first = self.samplers[0]
         if any(s.n_iterations != first.n_iterations for s in self.samplers):
@@ -77,10 +81,11 @@ class FusedBNNChains(object):
         eps = None
         for s in self.samplers:
             e = [next(s.stepsize_schedule) for _ in range(n_steps)]
-            if any(v != e[0] for v in e) or (eps is not None and e[0] != eps):
-                raise ValueError("FusedBNNChains.steps needs one constant stepsize for all chains over the chunk")
-            eps = e[0]
-            s.epsilon = eps
+            if eps is not None and e != eps:
+                raise ValueError("FusedBNNChains.steps needs one stepsize sequence for all chains over the chunk")
+            eps = e
+            s.epsilon = eps[-1]
+        table = first._fused_scalars_table(eps)
         gen, cost, a = first.batch_generator, first.cost_fun, first.arena
         starts = np.stack([s.batch_generator.next_starts(n_steps) for s in self.samplers]).astype(np.int32)
         starts = torch.as_tensor(starts).to(first.device).reshape(-1)
@@ -90,8 +95,8 @@ class FusedBNNChains(object):
         span = (self.n_chains - 1) * self.chain_stride + a.n
         bases = [torch.as_strided(self.storage, (span,), (1,), r.storage_offset() - self.storage.storage_offset())
                  for r in rows]
-        first._fused_bnn_launch(starts, costs, eps, n_steps, n_chains=self.n_chains, chain_stride=self.chain_stride,
-                                bases=bases)
+        first._fused_bnn_launch(starts, costs, eps[0], n_steps, n_chains=self.n_chains, chain_stride=self.chain_stride,
+                                bases=bases, **({} if table is None else {"scalars_steps": table}))
         costs = costs.view(self.n_chains, n_steps)
         for c, s in enumerate(self.samplers):
             s.n_iterations += n_steps

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from pysgmcmc_amd import kernels
+from pysgmcmc_amd.samplers._fused_bnn import FusedBNNStepsMixin
 from pysgmcmc_amd.samplers.base_classes import MCMCSampler
 from pysgmcmc_amd.stepsize_schedules import ConstantStepsizeSchedule
 
@@ -78,10 +79,11 @@ def _sample_relativistic_momentum(m, c, n_params, bounds=(float("-inf"), float("
     return out.clamp(lo, hi).to(dtype)
 
 
-class RelativisticSGHMCSampler(MCMCSampler):
+class RelativisticSGHMCSampler(FusedBNNStepsMixin, MCMCSampler):
     """Relativistic SGHMC (keywords/defaults as ``relativistic_sghmc.py:24-27``)."""
 
     _STATE_ROWS = ("p",)
+    _FUSED_ROWS = ("theta", "p", "grad")                                  # row order of the fused small-model kernel
 
     def __init__(self, params, cost_fun, batch_generator=None,
                  stepsize_schedule=ConstantStepsizeSchedule(0.001),
@@ -146,3 +148,13 @@ class RelativisticSGHMCSampler(MCMCSampler):
             *rows, eps, self.mass, self.speed_of_light, self.D, self.Bhat,
             xi=xi, stats=self._step_stats(), grad_decay=self._grad_decay, launch=self._launch(), opts=opts, **self._noise_args())
         self._stats_written()
+
+    # ------------------------------------------------------------------ fused small-model path (see _fused_bnn.py)
+    def _fused_bnn_launch(self, starts, costs, eps, n_steps, n_chains=1, chain_stride=None, bases=None, scalars_steps=None):
+        gen, cost, a = self.batch_generator, self.cost_fun, self.arena
+        rows = bases or [a.row(k) for k in self._FUSED_ROWS]
+        kernels.bnn_fused_rsghmc_steps(
+            *rows, self._bnn_layer_sizes(), gen.x_dev, gen.y_dev.reshape(-1), starts, gen.batch_size,
+            cost.batch_size, cost.n_examples, cost.wdecay, cost.prior_mean, cost.prior_var,
+            eps, self.mass, self.speed_of_light, self.D, self.Bhat, self.n_iterations, n_steps,
+            self._philox_seed, costs, n_chains=n_chains, chain_stride=chain_stride, scalars_steps=scalars_steps)
