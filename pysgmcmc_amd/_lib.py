@@ -136,10 +136,6 @@ def _declare(lib):
         f = getattr(lib, "sgmcmc_tanh_backward_" + sfx)
         f.argtypes = [_vp, _vp, _sz, _vp]
         f.restype = _ci
-        f = getattr(lib, "sgmcmc_bnn_fused_sghmc_steps_" + sfx)
-        f.argtypes = ([_vp] * 7 + [_sz, _sz, _ci, ctypes.POINTER(_ci), _ci, _vp, _vp, _sz, _vp, _ci]
-                      + [ctypes.c_double] * 5 + [real, real, real, _u64, _u64, _u64, _u64, _vp, _vp, _vp])
-        f.restype = _ci
         f = getattr(lib, "sgmcmc_bias_tanh_rowdot_" + sfx)
         f.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]
         f.restype = _ci
@@ -151,10 +147,6 @@ def _declare(lib):
         f.restype = _ci
         f = getattr(lib, "sgmcmc_window_gather_" + sfx)
         f.argtypes = [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _vp]
-        f.restype = _ci
-        f = getattr(lib, "sgmcmc_bnn_fused_sgld_steps_" + sfx)
-        f.argtypes = ([_vp] * 6 + [_sz, _sz, _ci, ctypes.POINTER(_ci), _ci, _vp, _vp, _sz, _vp, _ci]
-                      + [ctypes.c_double] * 5 + [real, real, real, _u64, _u64, _u64, _u64, _vp, _vp, _vp])
         f.restype = _ci
         f = getattr(lib, "sgmcmc_svgd_step_" + sfx)
         f.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, real, ctypes.c_double, real, _ci, _vp, _vp]
@@ -201,20 +193,25 @@ def _declare(lib):
         f.restype = _ci
     # include/sgmcmc_hip_fused.h
     lib.sgmcmc_fused_abi_version.restype = _ci
+    # The whole-step BNN kernel's entry points (sgmcmc_hip.h [whole-step] and sgmcmc_hip_fused.h): state rows, the net run
+    # n_params .. prior_var, the kind's by-value scalars (eps first), first_step, n_steps, [burn_in_steps,] seed_base, xi,
+    # cost_out, stream. A `sched` twin takes a required table where eps was; the relativistic entry an optional one after
+    # its scalars. kind: (rows, by-value scalars, burn_in_steps argument, sched twin)
+    net = [_sz, _sz, _ci, ctypes.POINTER(_ci), _ci, _vp, _vp, _sz, _vp, _ci] + [ctypes.c_double] * 5
+    whole_step = {"sghmc": (7, 3, True, True), "sgld": (6, 3, True, True), "rsghmc": (3, 5, False, False)}
     for sfx, real in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
-        net = [_sz, _sz, _ci, ctypes.POINTER(_ci), _ci, _vp, _vp, _sz, _vp, _ci] + [ctypes.c_double] * 5
-        for kind, n_scalars in (("sghmc", 2), ("sgld", 2), ("rsghmc", 4)):
+        for kind, (n_rows, n_scalars, burn_in, sched) in whole_step.items():
             f = getattr(lib, "sgmcmc_%s_scalars_steps_%s" % (kind, sfx))        # host pointers, nothing launched
-            f.argtypes = [ctypes.POINTER(real), _sz] + [real] * n_scalars + [ctypes.POINTER(real)]
+            f.argtypes = [ctypes.POINTER(real), _sz] + [real] * (n_scalars - 1) + [ctypes.POINTER(real)]
             f.restype = _ci
-        for kind, n_rows in (("sghmc", 7), ("sgld", 6)):
-            f = getattr(lib, "sgmcmc_bnn_fused_%s_sched_steps_%s" % (kind, sfx))
-            f.argtypes = [_vp] * n_rows + net + [_vp, real, real, _u64, _u64, _u64, _u64, _vp, _vp, _vp]
+            tail = [_u64] * (4 if burn_in else 3) + [_vp, _vp, _vp]
+            f = getattr(lib, "sgmcmc_bnn_fused_%s_steps_%s" % (kind, sfx))
+            f.argtypes = [_vp] * n_rows + net + [real] * n_scalars + ([] if sched else [_vp]) + tail
             f.restype = _ci
-        f = getattr(lib, "sgmcmc_bnn_fused_rsghmc_steps_" + sfx)
-        f.argtypes = [_vp] * 3 + net + [real] * 5 + [_vp, _u64, _u64, _u64, _vp, _vp, _vp]
-        f.restype = _ci
-
+            if sched:
+                f = getattr(lib, "sgmcmc_bnn_fused_%s_sched_steps_%s" % (kind, sfx))
+                f.argtypes = [_vp] * n_rows + net + [_vp] + [real] * (n_scalars - 1) + tail
+                f.restype = _ci
 
 def lib():
     """The loaded library (argtypes declared). Raises SgmcmcLibraryError if absent."""

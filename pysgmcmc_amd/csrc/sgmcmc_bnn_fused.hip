@@ -417,107 +417,106 @@ int launch_fused(const FusedArgs<T> &a, int n_chains, size_t lds_bytes, hipStrea
     return e == hipSuccess ? 0 : hip_fail(e, "launch bnn_fused_sghmc_kernel");
 }
 
-// `mom`: V (KIND 0), unused (KIND 1), p (KIND 2). `sc`: HOST block of the operator's five by-value scalars (sgmcmc_scalars.hpp).
-// `scalars_steps`: DEVICE table [n_steps][5] that replaces them step by step, or NULL; `need_table`: the entry point has no
-// by-value stepsize, so NULL is an error.
+// The 15 arguments every entry point shares, in the headers' order, as F(type, name): ONE list for the struct the entry
+// points pack them into, for their parameter lists and for the pack itself.
+#define FUSED_NET(F, T)                                                                                                    \
+    F(size_t, n_params) F(size_t, chain_stride) F(int, n_chains) F(const int *, layer_sizes) F(int, n_layers)              \
+    F(const T *, X) F(const T *, y) F(size_t, n_data) F(const int *, window_starts) F(int, batch) F(double, batch_size)    \
+    F(double, n_examples) F(double, wdecay) F(double, prior_mean) F(double, prior_var)
+#define FUSED_NET_FIELD(type, name) type name;
+#define FUSED_NET_PARAM(type, name) type name,
+#define FUSED_NET_ARG(type, name) name,
+#define FUSED_NET_PARAMS(T) FUSED_NET(FUSED_NET_PARAM, T)   /* ends with its comma: every entry point has parameters after it */
+#define FUSED_NET_PACK(T) FusedNet<T>{FUSED_NET(FUSED_NET_ARG, T)}
+
+template <typename T>
+struct FusedNet { FUSED_NET(FUSED_NET_FIELD, T) };
+
+// What the entry points of a KIND take and call themselves. Rows: SGHMC theta, V, grad, tau, g, v_hat, minv; SGLD the same
+// without V; relativistic theta, p, grad. Scalars: in the order of sgmcmc_<kind>_scalars_* (SGHMC eps, scale_grad, mdecay;
+// SGLD eps, A, scale_grad; relativistic eps, mass, c, D, b_hat). Names: by value, with a required table.
+constexpr int FUSED_N_ROWS[3] = {7, 6, 3};
+constexpr int FUSED_N_SCALARS[3] = {3, 3, 5};
+constexpr const char *FUSED_NAME[3][2] = {{"bnn_fused_sghmc_steps", "bnn_fused_sghmc_sched_steps"},
+                                          {"bnn_fused_sgld_steps", "bnn_fused_sgld_sched_steps"},
+                                          {"bnn_fused_rsghmc_steps", "bnn_fused_rsghmc_steps"}};
+
+// The one host path from every entry point to the launch. `by_value`: the scalars the operator's five by-value scalars are
+// derived from (sgmcmc_scalars.hpp). `scalars_steps`: DEVICE table [n_steps][5] that replaces those five step by step, or
+// NULL; `need_table`: the entry point has no by-value stepsize, so NULL is an error and `by_value` is not read.
 template <typename T, int KIND>
-int bnn_fused_steps(const char *what, T *theta, T *mom, T *grad, T *tau, T *g, T *v_hat, T *minv, size_t n_params,
-                    size_t chain_stride, int n_chains, const int *layer_sizes, int n_layers, const T *X, const T *y,
-                    size_t n_data, const int *window_starts, int batch, double batch_size, double n_examples, double wdecay,
-                    double prior_mean, double prior_var, const T (&sc)[5], const T *scalars_steps, bool need_table,
-                    uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base, const T *xi, T *cost_out,
-                    hipStream_t st)
+int bnn_fused_entry(T *const (&rows)[FUSED_N_ROWS[KIND]], const FusedNet<T> &n, const T (&by_value)[FUSED_N_SCALARS[KIND]],
+                    const T *scalars_steps, bool need_table, uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps,
+                    uint64_t seed_base, const T *xi, T *cost_out, sgmcmc_stream_t stream)
 {
-    if (n_steps == 0 || n_chains == 0) return 0;
-    const bool stats_rows = KIND != 2;                    // tau, g, v_hat, minv: the burn-in samplers' preconditioner state
-    if (!theta || (KIND != 1 && !mom) || !grad || (stats_rows && (!tau || !g || !v_hat || !minv)) || !layer_sizes || !X || !y ||
-        !window_starts || !cost_out)
+    const char *what = FUSED_NAME[KIND][need_table];
+    if (n_steps == 0 || n.n_chains == 0) return 0;
+    bool null_row = false;
+    for (T *p : rows) null_row |= !p;
+    if (null_row || !n.layer_sizes || !n.X || !n.y || !n.window_starts || !cost_out)
         return fail(SGMCMC_EINVAL, "%s: NULL argument", what);
     if (need_table && !scalars_steps) return fail(SGMCMC_EINVAL, "%s: scalars_steps is NULL", what);
-    if (n_layers < 1 || n_layers > FUSED_MAX_LAYERS) return fail(SGMCMC_EINVAL, "%s: 1..8 layers", what);
-    if (layer_sizes[n_layers] != 1) return fail(SGMCMC_EINVAL, "%s: the last layer must have one unit", what);
-    if (batch < 1 || (size_t)batch > n_data) return fail(SGMCMC_EINVAL, "%s: bad batch", what);
-    if (xi && (n_params % 4) != 0) return fail(SGMCMC_EINVAL, "%s: injected xi needs n_params %% 4 == 0", what);
-    if (n_chains > 1 && (chain_stride < n_params || (chain_stride % 4) != 0))
+    if (n.n_layers < 1 || n.n_layers > FUSED_MAX_LAYERS) return fail(SGMCMC_EINVAL, "%s: 1..8 layers", what);
+    if (n.layer_sizes[n.n_layers] != 1) return fail(SGMCMC_EINVAL, "%s: the last layer must have one unit", what);
+    if (n.batch < 1 || (size_t)n.batch > n.n_data) return fail(SGMCMC_EINVAL, "%s: bad batch", what);
+    if (xi && (n.n_params % 4) != 0) return fail(SGMCMC_EINVAL, "%s: injected xi needs n_params %% 4 == 0", what);
+    if (n.n_chains > 1 && (n.chain_stride < n.n_params || (n.chain_stride % 4) != 0))
         return fail(SGMCMC_EINVAL, "%s: chain_stride must be >= n_params and a multiple of 4", what);
-    T *rows[7] = {theta, KIND != 1 ? mom : theta, grad, stats_rows ? tau : theta, stats_rows ? g : theta,
-                  stats_rows ? v_hat : theta, stats_rows ? minv : theta};
     for (T *p : rows)
         if (reinterpret_cast<uintptr_t>(p) & 15u) return fail(SGMCMC_EINVAL, "%s: rows must be 16-B aligned", what);
-    FusedArgs<T> a{};
-    a.theta = theta; a.V = mom; a.grad = grad; a.tau = tau; a.g = g; a.vh = v_hat; a.minv = minv;
-    a.n_params = n_params; a.chain_stride = chain_stride; a.n_layers = n_layers;
-    size_t off = 0, lds_elems = 0;
-    for (int l = 0; l <= n_layers; ++l) {
-        if (layer_sizes[l] < 1) return fail(SGMCMC_EINVAL, "%s: bad layer size", what);
-        a.sizes[l] = layer_sizes[l];
+    FusedArgs<T> a{};                                     // the rows a KIND does not have stay NULL
+    if constexpr (KIND == 0) {
+        a.theta = rows[0]; a.V = rows[1]; a.grad = rows[2]; a.tau = rows[3]; a.g = rows[4]; a.vh = rows[5]; a.minv = rows[6];
+    } else if constexpr (KIND == 1) {
+        a.theta = rows[0]; a.grad = rows[1]; a.tau = rows[2]; a.g = rows[3]; a.vh = rows[4]; a.minv = rows[5];
+    } else {
+        a.theta = rows[0]; a.V = rows[1]; a.grad = rows[2];
     }
-    for (int l = 1; l <= n_layers; ++l) {                  // parameter order: W1, b1, ..., WL, bL, log_var
+    a.n_params = n.n_params; a.chain_stride = n.chain_stride; a.n_layers = n.n_layers;
+    size_t off = 0, lds_elems = 0;
+    for (int l = 0; l <= n.n_layers; ++l) {
+        if (n.layer_sizes[l] < 1) return fail(SGMCMC_EINVAL, "%s: bad layer size", what);
+        a.sizes[l] = n.layer_sizes[l];
+    }
+    for (int l = 1; l <= n.n_layers; ++l) {                // parameter order: W1, b1, ..., WL, bL, log_var
         a.off_w[l] = off; off += (size_t)a.sizes[l - 1] * a.sizes[l];
         a.off_b[l] = off; off += (size_t)a.sizes[l];
     }
-    if (off + 1 != n_params) return fail(SGMCMC_EINVAL, "%s: n_params does not match the layer sizes", what);
-    for (int l = 0; l <= n_layers; ++l) { a.act_off[l] = lds_elems; lds_elems += (size_t)batch * a.sizes[l]; }
+    if (off + 1 != n.n_params) return fail(SGMCMC_EINVAL, "%s: n_params does not match the layer sizes", what);
+    for (int l = 0; l <= n.n_layers; ++l) { a.act_off[l] = lds_elems; lds_elems += (size_t)n.batch * a.sizes[l]; }
     a.del_off[0] = 0;
-    for (int l = 1; l <= n_layers; ++l) { a.del_off[l] = lds_elems; lds_elems += (size_t)batch * a.sizes[l]; }
-    a.lds_y = lds_elems; lds_elems += (size_t)batch;
+    for (int l = 1; l <= n.n_layers; ++l) { a.del_off[l] = lds_elems; lds_elems += (size_t)n.batch * a.sizes[l]; }
+    a.lds_y = lds_elems; lds_elems += (size_t)n.batch;
     lds_elems = (lds_elems + 3) & ~(size_t)3;
-    a.lds_w = lds_elems; lds_elems += n_params;
+    a.lds_w = lds_elems; lds_elems += n.n_params;
     const size_t lds_bytes = 160 + lds_elems * sizeof(T);
     if (lds_bytes > 160 * 1024) return fail(SGMCMC_EINVAL, "%s: activations need %zu B of LDS (> 160 KiB); "
                                             "use the GEMM path", what, lds_bytes);
-    a.X = X; a.y = y; a.n_data = n_data; a.starts = window_starts; a.batch = batch;
-    a.batch_size = batch_size; a.n_examples = n_examples; a.wdecay = wdecay;
-    a.wp_den = (double)n_params + (2.0 * 1e-16 + 1e-16);
-    a.lvp_den = 2.0 * prior_var + (2.0 * 1e-16 + 1e-16);
-    a.ln_prior_mean = std::log(prior_mean); a.ln_prior_var = std::log(prior_var);
-    if (KIND == 0) { a.eps_e2 = sc[0]; a.c1 = sc[1]; a.c3 = sc[2]; a.e4 = sc[3]; a.mdecay = sc[4]; }
-    if (KIND == 1) { a.sgld_eps = sc[0]; a.sgld_A = sc[1]; a.sgld_a_eff = sc[2]; a.sgld_two_eps = sc[3]; a.sgld_den = sc[4]; }
-    if (KIND == 2) {
+    a.X = n.X; a.y = n.y; a.n_data = n.n_data; a.starts = n.window_starts; a.batch = n.batch;
+    a.batch_size = n.batch_size; a.n_examples = n.n_examples; a.wdecay = n.wdecay;
+    a.wp_den = (double)n.n_params + (2.0 * 1e-16 + 1e-16);
+    a.lvp_den = 2.0 * n.prior_var + (2.0 * 1e-16 + 1e-16);
+    a.ln_prior_mean = std::log(n.prior_mean); a.ln_prior_var = std::log(n.prior_var);
+    const T *v = by_value;
+    T sc[5] = {T(0), T(0), T(0), T(0), T(0)};
+    if constexpr (KIND == 0) {
+        if (!need_table) sghmc_scalars<T>(v[0], v[1], v[2], sc);
+        a.eps_e2 = sc[0]; a.c1 = sc[1]; a.c3 = sc[2]; a.e4 = sc[3]; a.mdecay = sc[4];
+    } else if constexpr (KIND == 1) {
+        if (!need_table) sgld_scalars<T>(v[0], v[1], v[2], sc);
+        a.sgld_eps = sc[0]; a.sgld_A = sc[1]; a.sgld_a_eff = sc[2]; a.sgld_two_eps = sc[3]; a.sgld_den = sc[4];
+    } else {
+        rsghmc_scalars<T>(v[0], v[1], v[2], v[3], v[4], sc);
         a.rs_eps = sc[0]; a.rs_mass = sc[1]; a.rs_D = sc[2]; a.rs_m2c2 = sc[3]; a.rs_nscale = sc[4];
         // POW2 as in sgmcmc_rsghmc.hip; not with a table, whose rows carry their own m2c2
         a.rs_pow2 = (rsghmc_m2c2_is_pow2<T>(sc[3], a.rs_inv) && !scalars_steps) ? 1 : 0;
     }
-    a.grad_decay = (T)(wdecay / (a.wp_den * n_examples));   // weight-prior gradient, folded into the update
+    a.grad_decay = (T)(n.wdecay / (a.wp_den * n.n_examples));   // weight-prior gradient, folded into the update
     a.first_step = first_step; a.n_steps = n_steps; a.burn_in_steps = burn_in_steps; a.seed_base = seed_base;
     a.xi = xi; a.cost_out = cost_out; a.scalars_steps = scalars_steps;
-    return scalars_steps ? launch_fused<T, KIND, true>(a, n_chains, lds_bytes, st)
-                         : launch_fused<T, KIND, false>(a, n_chains, lds_bytes, st);
-}
-
-// the existing by-value entry points and their table twins: SGHMC (eps, scale_grad, mdecay), SGLD (eps, scale_grad, A)
-template <typename T, int KIND>
-int bnn_fused_burn_in_steps(const char *what, T *theta, T *V, T *grad, T *tau, T *g, T *v_hat, T *minv, size_t n_params,
-                            size_t chain_stride, int n_chains, const int *layer_sizes, int n_layers, const T *X, const T *y,
-                            size_t n_data, const int *window_starts, int batch, double batch_size, double n_examples,
-                            double wdecay, double prior_mean, double prior_var, T eps, T scale_grad, T mdecay_or_A,
-                            const T *scalars_steps, bool need_table, uint64_t first_step, uint64_t n_steps,
-                            uint64_t burn_in_steps, uint64_t seed_base, const T *xi, T *cost_out, sgmcmc_stream_t stream)
-{
-    T sc[5] = {T(0), T(0), T(0), T(0), T(0)};
-    if (!need_table) {
-        if (KIND == 0) sghmc_scalars<T>(eps, scale_grad, mdecay_or_A, sc);
-        else sgld_scalars<T>(eps, mdecay_or_A, scale_grad, sc);
-    }
-    return bnn_fused_steps<T, KIND>(what, theta, V, grad, tau, g, v_hat, minv, n_params, chain_stride, n_chains, layer_sizes,
-                                    n_layers, X, y, n_data, window_starts, batch, batch_size, n_examples, wdecay, prior_mean,
-                                    prior_var, sc, scalars_steps, need_table, first_step, n_steps, burn_in_steps, seed_base, xi,
-                                    cost_out, static_cast<hipStream_t>(stream));
-}
-
-template <typename T>
-int bnn_fused_rsghmc(T *theta, T *p, T *grad, size_t n_params, size_t chain_stride, int n_chains, const int *layer_sizes,
-                     int n_layers, const T *X, const T *y, size_t n_data, const int *window_starts, int batch,
-                     double batch_size, double n_examples, double wdecay, double prior_mean, double prior_var, T eps, T mass,
-                     T c, T D, T b_hat, const T *scalars_steps, uint64_t first_step, uint64_t n_steps, uint64_t seed_base,
-                     const T *xi, T *cost_out, sgmcmc_stream_t stream)
-{
-    T sc[5];
-    rsghmc_scalars<T>(eps, mass, c, D, b_hat, sc);
-    return bnn_fused_steps<T, 2>("bnn_fused_rsghmc_steps", theta, p, grad, nullptr, nullptr, nullptr, nullptr, n_params,
-                                 chain_stride, n_chains, layer_sizes, n_layers, X, y, n_data, window_starts, batch, batch_size,
-                                 n_examples, wdecay, prior_mean, prior_var, sc, scalars_steps, false, first_step, n_steps, 0,
-                                 seed_base, xi, cost_out, static_cast<hipStream_t>(stream));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return scalars_steps ? launch_fused<T, KIND, true>(a, n.n_chains, lds_bytes, st)
+                         : launch_fused<T, KIND, false>(a, n.n_chains, lds_bytes, st);
 }
 
 // HOST table [n_steps][5] of an operator's scalars for the stepsizes eps[0 .. n_steps): `derive(eps, row)` is the shared derivation
@@ -536,52 +535,37 @@ int scalars_steps_fill(const char *what, const T *eps, size_t n_steps, T *block,
 
 }  // namespace
 
-#define FUSED_COMMON_PARAMS(T)                                                                                             \
-    size_t n_params, size_t chain_stride, int n_chains, const int *layer_sizes, int n_layers, const T *X, const T *y,      \
-    size_t n_data, const int *window_starts, int batch, double batch_size, double n_examples, double wdecay,               \
-    double prior_mean, double prior_var
-#define FUSED_COMMON_ARGS                                                                                                   \
-    n_params, chain_stride, n_chains, layer_sizes, n_layers, X, y, n_data, window_starts, batch, batch_size, n_examples,    \
-    wdecay, prior_mean, prior_var
+// Each entry point packs its arguments and names its kind. The f32 and f64 twins of a signature are stamped from one text,
+// the ENTRY(SFX, T) defined just above each FUSED_TWINS.
+#define FUSED_TWINS ENTRY(f32, float) ENTRY(f64, double)
 
 extern "C" {
 
-int sgmcmc_bnn_fused_sghmc_steps_f32(float *theta, float *V, float *grad, float *tau, float *g, float *v_hat, float *minv,
-                                     FUSED_COMMON_PARAMS(float), float eps, float scale_grad, float mdecay,
-                                     uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base,
-                                     const float *xi, float *cost_out, sgmcmc_stream_t stream)
-{
-    return bnn_fused_burn_in_steps<float, 0>("bnn_fused_sghmc_steps", theta, V, grad, tau, g, v_hat, minv, FUSED_COMMON_ARGS,
-                                             eps, scale_grad, mdecay, nullptr, false, first_step, n_steps, burn_in_steps,
-                                             seed_base, xi, cost_out, stream);
-}
-int sgmcmc_bnn_fused_sghmc_steps_f64(double *theta, double *V, double *grad, double *tau, double *g, double *v_hat,
-                                     double *minv, FUSED_COMMON_PARAMS(double), double eps, double scale_grad, double mdecay,
-                                     uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base,
-                                     const double *xi, double *cost_out, sgmcmc_stream_t stream)
-{
-    return bnn_fused_burn_in_steps<double, 0>("bnn_fused_sghmc_steps", theta, V, grad, tau, g, v_hat, minv, FUSED_COMMON_ARGS,
-                                              eps, scale_grad, mdecay, nullptr, false, first_step, n_steps, burn_in_steps,
-                                              seed_base, xi, cost_out, stream);
-}
-int sgmcmc_bnn_fused_sgld_steps_f32(float *theta, float *grad, float *tau, float *g, float *v_hat, float *minv,
-                                    FUSED_COMMON_PARAMS(float), float eps, float scale_grad, float A, uint64_t first_step,
-                                    uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base, const float *xi,
-                                    float *cost_out, sgmcmc_stream_t stream)
-{
-    return bnn_fused_burn_in_steps<float, 1>("bnn_fused_sghmc_steps", theta, nullptr, grad, tau, g, v_hat, minv,
-                                             FUSED_COMMON_ARGS, eps, scale_grad, A, nullptr, false, first_step, n_steps,
-                                             burn_in_steps, seed_base, xi, cost_out, stream);
-}
-int sgmcmc_bnn_fused_sgld_steps_f64(double *theta, double *grad, double *tau, double *g, double *v_hat, double *minv,
-                                    FUSED_COMMON_PARAMS(double), double eps, double scale_grad, double A, uint64_t first_step,
-                                    uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base, const double *xi,
-                                    double *cost_out, sgmcmc_stream_t stream)
-{
-    return bnn_fused_burn_in_steps<double, 1>("bnn_fused_sghmc_steps", theta, nullptr, grad, tau, g, v_hat, minv,
-                                              FUSED_COMMON_ARGS, eps, scale_grad, A, nullptr, false, first_step, n_steps,
-                                              burn_in_steps, seed_base, xi, cost_out, stream);
-}
+// ---- include/sgmcmc_hip.h, [whole-step]: one by-value stepsize per launch
+
+#define ENTRY(SFX, T)                                                                                                      \
+    int sgmcmc_bnn_fused_sghmc_steps_##SFX(T *theta, T *V, T *grad, T *tau, T *g, T *v_hat, T *minv, FUSED_NET_PARAMS(T)   \
+                                           T eps, T scale_grad, T mdecay, uint64_t first_step, uint64_t n_steps,           \
+                                           uint64_t burn_in_steps, uint64_t seed_base, const T *xi, T *cost_out,           \
+                                           sgmcmc_stream_t stream)                                                         \
+    {                                                                                                                      \
+        return bnn_fused_entry<T, 0>({theta, V, grad, tau, g, v_hat, minv}, FUSED_NET_PACK(T), {eps, scale_grad, mdecay},  \
+                                     nullptr, false, first_step, n_steps, burn_in_steps, seed_base, xi, cost_out, stream); \
+    }
+FUSED_TWINS
+#undef ENTRY
+
+#define ENTRY(SFX, T)                                                                                                      \
+    int sgmcmc_bnn_fused_sgld_steps_##SFX(T *theta, T *grad, T *tau, T *g, T *v_hat, T *minv, FUSED_NET_PARAMS(T) T eps,   \
+                                          T scale_grad, T A, uint64_t first_step, uint64_t n_steps,                        \
+                                          uint64_t burn_in_steps, uint64_t seed_base, const T *xi, T *cost_out,            \
+                                          sgmcmc_stream_t stream)                                                          \
+    {                                                                                                                      \
+        return bnn_fused_entry<T, 1>({theta, grad, tau, g, v_hat, minv}, FUSED_NET_PACK(T), {eps, A, scale_grad}, nullptr, \
+                                     false, first_step, n_steps, burn_in_steps, seed_base, xi, cost_out, stream);          \
+    }
+FUSED_TWINS
+#undef ENTRY
 
 // ---- include/sgmcmc_hip_fused.h
 
@@ -620,60 +604,42 @@ int sgmcmc_rsghmc_scalars_steps_f64(const double *eps_host, size_t n_steps, doub
                                       [=](double e, double (&s)[5]) { rsghmc_scalars<double>(e, mass, c, D, b_hat, s); });
 }
 
-int sgmcmc_bnn_fused_sghmc_sched_steps_f32(float *theta, float *V, float *grad, float *tau, float *g, float *v_hat,
-                                           float *minv, FUSED_COMMON_PARAMS(float), const float *scalars_steps,
-                                           float scale_grad, float mdecay, uint64_t first_step, uint64_t n_steps,
-                                           uint64_t burn_in_steps, uint64_t seed_base, const float *xi, float *cost_out,
-                                           sgmcmc_stream_t stream)
-{
-    return bnn_fused_burn_in_steps<float, 0>("bnn_fused_sghmc_sched_steps", theta, V, grad, tau, g, v_hat, minv,
-                                             FUSED_COMMON_ARGS, 0.0f, scale_grad, mdecay, scalars_steps, true, first_step,
-                                             n_steps, burn_in_steps, seed_base, xi, cost_out, stream);
-}
-int sgmcmc_bnn_fused_sghmc_sched_steps_f64(double *theta, double *V, double *grad, double *tau, double *g, double *v_hat,
-                                           double *minv, FUSED_COMMON_PARAMS(double), const double *scalars_steps,
-                                           double scale_grad, double mdecay, uint64_t first_step, uint64_t n_steps,
-                                           uint64_t burn_in_steps, uint64_t seed_base, const double *xi, double *cost_out,
-                                           sgmcmc_stream_t stream)
-{
-    return bnn_fused_burn_in_steps<double, 0>("bnn_fused_sghmc_sched_steps", theta, V, grad, tau, g, v_hat, minv,
-                                              FUSED_COMMON_ARGS, 0.0, scale_grad, mdecay, scalars_steps, true, first_step,
-                                              n_steps, burn_in_steps, seed_base, xi, cost_out, stream);
-}
-int sgmcmc_bnn_fused_sgld_sched_steps_f32(float *theta, float *grad, float *tau, float *g, float *v_hat, float *minv,
-                                          FUSED_COMMON_PARAMS(float), const float *scalars_steps, float scale_grad, float A,
-                                          uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base,
-                                          const float *xi, float *cost_out, sgmcmc_stream_t stream)
-{
-    return bnn_fused_burn_in_steps<float, 1>("bnn_fused_sgld_sched_steps", theta, nullptr, grad, tau, g, v_hat, minv,
-                                             FUSED_COMMON_ARGS, 0.0f, scale_grad, A, scalars_steps, true, first_step, n_steps,
-                                             burn_in_steps, seed_base, xi, cost_out, stream);
-}
-int sgmcmc_bnn_fused_sgld_sched_steps_f64(double *theta, double *grad, double *tau, double *g, double *v_hat, double *minv,
-                                          FUSED_COMMON_PARAMS(double), const double *scalars_steps, double scale_grad,
-                                          double A, uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps,
-                                          uint64_t seed_base, const double *xi, double *cost_out, sgmcmc_stream_t stream)
-{
-    return bnn_fused_burn_in_steps<double, 1>("bnn_fused_sgld_sched_steps", theta, nullptr, grad, tau, g, v_hat, minv,
-                                              FUSED_COMMON_ARGS, 0.0, scale_grad, A, scalars_steps, true, first_step, n_steps,
-                                              burn_in_steps, seed_base, xi, cost_out, stream);
-}
+// `scale_grad` and `mdecay` / `A` keep their places and are not read: the table's rows carry what is derived from them
+#define ENTRY(SFX, T)                                                                                                      \
+    int sgmcmc_bnn_fused_sghmc_sched_steps_##SFX(T *theta, T *V, T *grad, T *tau, T *g, T *v_hat, T *minv,                 \
+                                                 FUSED_NET_PARAMS(T) const T *scalars_steps, T scale_grad, T mdecay,       \
+                                                 uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps,            \
+                                                 uint64_t seed_base, const T *xi, T *cost_out, sgmcmc_stream_t stream)     \
+    {                                                                                                                      \
+        return bnn_fused_entry<T, 0>({theta, V, grad, tau, g, v_hat, minv}, FUSED_NET_PACK(T), {T(0), scale_grad, mdecay}, \
+                                     scalars_steps, true, first_step, n_steps, burn_in_steps, seed_base, xi, cost_out,     \
+                                     stream);                                                                              \
+    }
+FUSED_TWINS
+#undef ENTRY
 
-int sgmcmc_bnn_fused_rsghmc_steps_f32(float *theta, float *p, float *grad, FUSED_COMMON_PARAMS(float), float eps, float mass,
-                                      float c, float D, float b_hat, const float *scalars_steps, uint64_t first_step,
-                                      uint64_t n_steps, uint64_t seed_base, const float *xi, float *cost_out,
-                                      sgmcmc_stream_t stream)
-{
-    return bnn_fused_rsghmc<float>(theta, p, grad, FUSED_COMMON_ARGS, eps, mass, c, D, b_hat, scalars_steps, first_step,
-                                   n_steps, seed_base, xi, cost_out, stream);
-}
-int sgmcmc_bnn_fused_rsghmc_steps_f64(double *theta, double *p, double *grad, FUSED_COMMON_PARAMS(double), double eps,
-                                      double mass, double c, double D, double b_hat, const double *scalars_steps,
-                                      uint64_t first_step, uint64_t n_steps, uint64_t seed_base, const double *xi,
-                                      double *cost_out, sgmcmc_stream_t stream)
-{
-    return bnn_fused_rsghmc<double>(theta, p, grad, FUSED_COMMON_ARGS, eps, mass, c, D, b_hat, scalars_steps, first_step,
-                                    n_steps, seed_base, xi, cost_out, stream);
-}
+#define ENTRY(SFX, T)                                                                                                      \
+    int sgmcmc_bnn_fused_sgld_sched_steps_##SFX(T *theta, T *grad, T *tau, T *g, T *v_hat, T *minv, FUSED_NET_PARAMS(T)    \
+                                                const T *scalars_steps, T scale_grad, T A, uint64_t first_step,            \
+                                                uint64_t n_steps, uint64_t burn_in_steps, uint64_t seed_base,              \
+                                                const T *xi, T *cost_out, sgmcmc_stream_t stream)                          \
+    {                                                                                                                      \
+        return bnn_fused_entry<T, 1>({theta, grad, tau, g, v_hat, minv}, FUSED_NET_PACK(T), {T(0), A, scale_grad},         \
+                                     scalars_steps, true, first_step, n_steps, burn_in_steps, seed_base, xi, cost_out,     \
+                                     stream);                                                                              \
+    }
+FUSED_TWINS
+#undef ENTRY
+
+#define ENTRY(SFX, T)                                                                                                      \
+    int sgmcmc_bnn_fused_rsghmc_steps_##SFX(T *theta, T *p, T *grad, FUSED_NET_PARAMS(T) T eps, T mass, T c, T D, T b_hat, \
+                                            const T *scalars_steps, uint64_t first_step, uint64_t n_steps,                 \
+                                            uint64_t seed_base, const T *xi, T *cost_out, sgmcmc_stream_t stream)          \
+    {                                                                                                                      \
+        return bnn_fused_entry<T, 2>({theta, p, grad}, FUSED_NET_PACK(T), {eps, mass, c, D, b_hat}, scalars_steps, false,  \
+                                     first_step, n_steps, 0, seed_base, xi, cost_out, stream);                             \
+    }
+FUSED_TWINS
+#undef ENTRY
 
 }  // extern "C"

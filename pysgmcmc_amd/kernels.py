@@ -16,7 +16,7 @@ __all__ = [
     "sghmc_step", "sgld_step", "rsghmc_step", "philox_normal", "philox_bits",
     "moments_update", "rhat_pack", "rhat_finish", "summary",
     "LaunchConfig", "KernelEvents", "StepOpts", "step_stats_records", "step_scalars", "toy_chains", "set_launch_config", "get_launch_config", "summary_workspace", "counter_add", "StepStats", "bnn_head", "bnn_dense_tanh_backward", "bnn_dense_tanh_backward_fits", "colsum_finish", "tanh_backward", "tanh_backward_colsum", "bnn_last_layer_backward", "bnn_fused_sghmc_steps", "step_stats_finish",
-    "bnn_fused_sgld_steps", "bnn_fused_rsghmc_steps", "step_scalars_table", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
+    "bnn_fused_sgld_steps", "bnn_fused_rsghmc_steps", "bnn_fused_steps", "step_scalars_table", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
     "ess_variogram",
 ]
 
@@ -522,30 +522,6 @@ def bnn_last_layer_backward(dvec, w, h, delta_prev, colsum, gw, bias_prev=None, 
     check(rc, "sgmcmc_bnn_last_layer_backward")
 
 
-def _fused_net_args(theta, layer_sizes, X, y, window_starts, batch, batch_size, n_examples, wdecay, prior_mean, prior_var,
-                    n_steps, n_chains, chain_stride):
-    """The argument run every whole-step entry point shares: ``n_params .. prior_var`` (and the array that keeps the
-    layer sizes alive during the call)."""
-    import ctypes
-    sizes = [int(v) for v in layer_sizes]
-    n_layers = len(sizes) - 1
-    n_params = sum(sizes[l] * sizes[l + 1] + sizes[l + 1] for l in range(n_layers)) + 1
-    if chain_stride is None:
-        chain_stride = theta.numel() if n_chains == 1 else theta.numel() // n_chains
-    if window_starts.dtype != torch.int32 or window_starts.numel() != n_chains * n_steps:
-        raise TypeError("window_starts must be an int32 device tensor of n_chains * n_steps entries")
-    arr = (ctypes.c_int * len(sizes))(*sizes)
-    return (n_params, int(chain_stride), int(n_chains), arr, n_layers, _ptr(X), _ptr(y), int(X.shape[0]),
-            _ptr(window_starts), int(batch), float(batch_size), float(n_examples), float(wdecay), float(prior_mean),
-            float(prior_var))
-
-
-def _table_ptr(scalars_steps, like, n_steps):
-    if scalars_steps.dtype != like.dtype or scalars_steps.numel() != 5 * int(n_steps):
-        raise TypeError("scalars_steps must hold n_steps x 5 elements of the step's dtype (kernels.step_scalars_table)")
-    return _ptr(scalars_steps)
-
-
 def step_scalars_table(kind, eps_list, *scalars, dtype, device):
     """Device table ``[len(eps_list), 5]`` of a whole-step launch's per-step scalars (``scalars_steps=``): row ``t`` is the
     block ``step_scalars`` makes for stepsize ``eps_list[t]``. ``scalars`` are the sampler's other scalars in the order of
@@ -564,6 +540,45 @@ def step_scalars_table(kind, eps_list, *scalars, dtype, device):
     return torch.from_numpy(block).to(device)
 
 
+# kind -> (where the C entry's scalars after eps stand in the sampler's ``scalars``; a burn-in sampler's entry, which has a
+# ``burn_in_steps`` argument and a ``sched`` twin for a table, where the relativistic entry takes the table as an option)
+_FUSED_KINDS = {"sghmc": ((1, 2), True), "sgld": ((2, 1), True), "rsghmc": ((1, 2, 3, 4), False)}
+
+
+def bnn_fused_steps(kind, rows, layer_sizes, X, y, window_starts, batch, batch_size, n_examples, wdecay, prior_mean,
+                    prior_var, scalars, first_step, n_steps, burn_in_steps, seed_base, cost_out, xi=None, n_chains=1,
+                    chain_stride=None, scalars_steps=None):
+    """``n_steps`` complete steps of a small tanh-MLP BNN per chain in one launch, whichever the update: ``kind`` "sghmc",
+    "sgld" or "rsghmc", ``rows`` the kind's state rows in the entry's order, ``scalars`` the sampler's scalars in the order
+    of ``step_scalars`` (``eps`` first). ``scalars_steps`` (``step_scalars_table(kind, ...)``) replaces ``eps`` step by
+    step; ``burn_in_steps`` is ignored for "rsghmc". The one caller of ``sgmcmc_bnn_fused_*_steps_*``."""
+    import ctypes
+    if kind not in _FUSED_KINDS:
+        raise ValueError("bnn_fused_steps: kind must be one of %s, not %r" % (", ".join(sorted(_FUSED_KINDS)), kind))
+    order, burn_in = _FUSED_KINDS[kind]
+    theta, sched = rows[0], burn_in and scalars_steps is not None
+    name = "sgmcmc_bnn_fused_%s_%ssteps" % (kind, "sched_" if sched else "")
+    f = getattr(lib(), "%s_%s" % (name, _sfx(theta)))
+    sizes = [int(v) for v in layer_sizes]
+    n_params = sum(sizes[l] * sizes[l + 1] + sizes[l + 1] for l in range(len(sizes) - 1)) + 1
+    if chain_stride is None:
+        chain_stride = theta.numel() if n_chains == 1 else theta.numel() // n_chains
+    if window_starts.dtype != torch.int32 or window_starts.numel() != n_chains * n_steps:
+        raise TypeError("window_starts must be an int32 device tensor of n_chains * n_steps entries")
+    if scalars_steps is not None and (scalars_steps.dtype != theta.dtype or scalars_steps.numel() != 5 * int(n_steps)):
+        raise TypeError("scalars_steps must hold n_steps x 5 elements of the step's dtype (kernels.step_scalars_table)")
+    other = [float(scalars[i]) for i in order]
+    by_value = [_ptr(scalars_steps)] + other if sched else [float(scalars[0])] + other
+    with _on(theta):
+        rc = f(*[_ptr(r) for r in rows], n_params, int(chain_stride), int(n_chains), (ctypes.c_int * len(sizes))(*sizes),
+               len(sizes) - 1, _ptr(X), _ptr(y), int(X.shape[0]), _ptr(window_starts), int(batch), float(batch_size),
+               float(n_examples), float(wdecay), float(prior_mean), float(prior_var), *by_value,
+               *([] if burn_in else [_ptr(scalars_steps)]), int(first_step), int(n_steps),
+               *([int(burn_in_steps)] if burn_in else []), int(seed_base), _ptr(xi), _ptr(cost_out), _stream(theta))
+    check(rc, name)
+    return cost_out
+
+
 def bnn_fused_sghmc_steps(theta, V, grad, tau, g, v_hat, minv, layer_sizes, X, y, window_starts, batch,
                           batch_size, n_examples, wdecay, prior_mean, prior_var, eps, scale_grad, mdecay,
                           first_step, n_steps, burn_in_steps, seed_base, cost_out, xi=None, n_chains=1,
@@ -572,17 +587,9 @@ def bnn_fused_sghmc_steps(theta, V, grad, tau, g, v_hat, minv, layer_sizes, X, y
     include/sgmcmc_hip.h). Rows are ``(n_chains * chain_stride,)`` or, for one chain, ``(n_params,)``.
     ``scalars_steps`` (``step_scalars_table("sghmc", ...)``): a stepsize per step instead of ``eps``
     (``sgmcmc_bnn_fused_sghmc_sched_steps_*``, include/sgmcmc_hip_fused.h)."""
-    sched = scalars_steps is not None
-    f = getattr(lib(), "sgmcmc_bnn_fused_sghmc_%ssteps_%s" % ("sched_" if sched else "", _sfx(theta)))
-    net = _fused_net_args(theta, layer_sizes, X, y, window_starts, batch, batch_size, n_examples, wdecay, prior_mean,
-                          prior_var, n_steps, n_chains, chain_stride)
-    with _on(theta):
-        rc = f(_ptr(theta), _ptr(V), _ptr(grad), _ptr(tau), _ptr(g), _ptr(v_hat), _ptr(minv), *net,
-               _table_ptr(scalars_steps, theta, n_steps) if sched else float(eps), float(scale_grad), float(mdecay),
-               int(first_step), int(n_steps), int(burn_in_steps), int(seed_base), _ptr(xi), _ptr(cost_out),
-               _stream(theta))
-    check(rc, "sgmcmc_bnn_fused_sghmc_%ssteps" % ("sched_" if sched else ""))
-    return cost_out
+    return bnn_fused_steps("sghmc", (theta, V, grad, tau, g, v_hat, minv), layer_sizes, X, y, window_starts, batch,
+                           batch_size, n_examples, wdecay, prior_mean, prior_var, (eps, scale_grad, mdecay), first_step,
+                           n_steps, burn_in_steps, seed_base, cost_out, xi, n_chains, chain_stride, scalars_steps)
 
 
 def bnn_fused_sgld_steps(theta, grad, tau, g, v_hat, minv, layer_sizes, X, y, window_starts, batch,
@@ -591,17 +598,9 @@ def bnn_fused_sgld_steps(theta, grad, tau, g, v_hat, minv, layer_sizes, X, y, wi
                          chain_stride=None, scalars_steps=None):
     """The fused small-model kernel with the preconditioned-SGLD update (``sgmcmc_bnn_fused_sgld_steps_*``;
     with ``scalars_steps`` from ``step_scalars_table("sgld", ...)``: ``sgmcmc_bnn_fused_sgld_sched_steps_*``)."""
-    sched = scalars_steps is not None
-    f = getattr(lib(), "sgmcmc_bnn_fused_sgld_%ssteps_%s" % ("sched_" if sched else "", _sfx(theta)))
-    net = _fused_net_args(theta, layer_sizes, X, y, window_starts, batch, batch_size, n_examples, wdecay, prior_mean,
-                          prior_var, n_steps, n_chains, chain_stride)
-    with _on(theta):
-        rc = f(_ptr(theta), _ptr(grad), _ptr(tau), _ptr(g), _ptr(v_hat), _ptr(minv), *net,
-               _table_ptr(scalars_steps, theta, n_steps) if sched else float(eps), float(scale_grad), float(A),
-               int(first_step), int(n_steps), int(burn_in_steps), int(seed_base), _ptr(xi), _ptr(cost_out),
-               _stream(theta))
-    check(rc, "sgmcmc_bnn_fused_sgld_%ssteps" % ("sched_" if sched else ""))
-    return cost_out
+    return bnn_fused_steps("sgld", (theta, grad, tau, g, v_hat, minv), layer_sizes, X, y, window_starts, batch,
+                           batch_size, n_examples, wdecay, prior_mean, prior_var, (eps, A, scale_grad), first_step,
+                           n_steps, burn_in_steps, seed_base, cost_out, xi, n_chains, chain_stride, scalars_steps)
 
 
 def bnn_fused_rsghmc_steps(theta, p, grad, layer_sizes, X, y, window_starts, batch, batch_size, n_examples, wdecay,
@@ -610,15 +609,9 @@ def bnn_fused_rsghmc_steps(theta, p, grad, layer_sizes, X, y, window_starts, bat
     """The fused small-model kernel with the relativistic SGHMC update (``sgmcmc_bnn_fused_rsghmc_steps_*``,
     include/sgmcmc_hip_fused.h): rows ``theta, p, grad``, no burn-in switch. ``scalars_steps``
     (``step_scalars_table("rsghmc", ...)``) replaces the by-value stepsize step by step."""
-    f = getattr(lib(), "sgmcmc_bnn_fused_rsghmc_steps_" + _sfx(theta))
-    net = _fused_net_args(theta, layer_sizes, X, y, window_starts, batch, batch_size, n_examples, wdecay, prior_mean,
-                          prior_var, n_steps, n_chains, chain_stride)
-    with _on(theta):
-        rc = f(_ptr(theta), _ptr(p), _ptr(grad), *net, float(eps), float(mass), float(c), float(D), float(b_hat),
-               None if scalars_steps is None else _table_ptr(scalars_steps, theta, n_steps),
-               int(first_step), int(n_steps), int(seed_base), _ptr(xi), _ptr(cost_out), _stream(theta))
-    check(rc, "sgmcmc_bnn_fused_rsghmc_steps")
-    return cost_out
+    return bnn_fused_steps("rsghmc", (theta, p, grad), layer_sizes, X, y, window_starts, batch, batch_size, n_examples,
+                           wdecay, prior_mean, prior_var, (eps, mass, c, D, b_hat), first_step, n_steps, 0, seed_base,
+                           cost_out, xi, n_chains, chain_stride, scalars_steps)
 
 
 def bias_tanh(a, bias):

@@ -1,6 +1,11 @@
 """Whole steps of a small BNN in one kernel (csrc/sgmcmc_bnn_fused.hip), shared by the samplers of the hot path:
 SGHMC and SGLD (the two the reference's BNN accepts, ``pysgmcmc/sampling.py:40,64``) and relativistic SGHMC.
 
+A sampler supplies four hooks and nothing else: ``_FUSED_ROWS`` (its state rows in the kernel's order), ``_SCALARS_KIND``
+(which update operator), ``_step_scalars(eps)`` (the operator's scalars, ``eps`` first) and, if it has a burn-in,
+``burn_in_steps``. From there ONE path leads to the launch (``_fused_bnn_launch`` -> ``kernels.bnn_fused_steps``), for one
+chain (``fused_bnn_steps``) and for a group (``fused_chains.FusedBNNChains.steps``).
+
 The stepsize may move inside a chunk: the kernel then reads each step's derived scalars from a device table built on the
 host from the schedule's values (``kernels.step_scalars_table``); a chunk at one stepsize is launched by value."""
 import numpy as np
@@ -12,8 +17,7 @@ __all__ = ("FusedBNNStepsMixin",)
 
 
 class FusedBNNStepsMixin(object):
-    """``fused_bnn_available()`` / ``fused_bnn_steps(n)``; the sampler supplies ``_FUSED_ROWS``, ``_SCALARS_KIND`` /
-    ``_step_scalars(eps)`` and ``_fused_bnn_launch(starts, costs, eps, n_steps, ..., scalars_steps=None)``."""
+    """``fused_bnn_available()`` / ``fused_bnn_steps(n)`` from the four hooks of the module docstring."""
 
     def fused_bnn_available(self):
         """True when whole steps can run inside ONE kernel (``sgmcmc_bnn_fused_{sghmc,sgld,rsghmc}_steps``): the cost is
@@ -52,6 +56,37 @@ class FusedBNNStepsMixin(object):
         return kernels.step_scalars_table(self._SCALARS_KIND, eps, *self._step_scalars(eps[0])[1:],
                                           dtype=self._torch_dtype, device=self.device)
 
+    def _fused_stepsizes(self, n_steps):
+        """The chunk's ``n_steps`` stepsizes, drawn from the schedule up front; ``epsilon`` ends as the last one."""
+        eps = [next(self.stepsize_schedule) for _ in range(n_steps)]
+        self.epsilon = eps[-1]
+        return eps
+
+    def _fused_window_starts(self, n_steps):
+        """The chunk's ``n_steps`` window starts (host, int32): first a window ``next(sampler)`` drew one step ahead
+        (``base_classes._window_to_prefetch``) or a resumed chain carries (``load_state_dict``), then the generator's."""
+        pending, self._pending_window = getattr(self, "_pending_window", None), None
+        if pending is None:
+            return self.batch_generator.next_starts(n_steps)
+        return np.concatenate([np.asarray([pending[0]], dtype=np.int32), self.batch_generator.next_starts(n_steps - 1)])
+
+    def _fused_bnn_launch(self, starts, costs, eps, n_steps, n_chains=1, chain_stride=None, bases=None, scalars_steps=None):
+        """Launch ``n_steps`` steps at stepsize ``eps`` (or the table's) on this chain's rows, or on ``bases`` for a group."""
+        gen, cost, a = self.batch_generator, self.cost_fun, self.arena
+        kernels.bnn_fused_steps(
+            self._SCALARS_KIND, bases or [a.row(k) for k in self._FUSED_ROWS], self._bnn_layer_sizes(), gen.x_dev,
+            gen.y_dev.reshape(-1), starts, gen.batch_size, cost.batch_size, cost.n_examples, cost.wdecay, cost.prior_mean,
+            cost.prior_var, self._step_scalars(eps), self.n_iterations, n_steps, max(getattr(self, "burn_in_steps", 0), 0),
+            self._philox_seed, costs, n_chains=n_chains, chain_stride=chain_stride, scalars_steps=scalars_steps)
+
+    def _fused_steps_done(self, n_steps, last_cost):
+        """The chain's bookkeeping after a launch that advanced it by ``n_steps``."""
+        cost = self.cost_fun
+        self.n_iterations += n_steps
+        self._stats_valid = False                 # theta moved without the statistics workspace
+        self._grad_decay = float(cost.wdecay / ((self.arena.n + 3e-16) * cost.n_examples))
+        self.cost = last_cost
+
     def fused_bnn_steps(self, n_steps):
         """Advance the chain by ``n_steps`` complete steps in one launch (one workgroup; see
         ``csrc/sgmcmc_bnn_fused.hip``). Same chain as ``n_steps`` calls of ``next()`` up to the rounding of
@@ -64,24 +99,9 @@ class FusedBNNStepsMixin(object):
         if not self.fused_bnn_available():
             raise ValueError("fused_bnn_steps: this sampler/cost/batch generator does not fit the fused small-model kernel")
         n_steps = int(n_steps)
-        eps = [next(self.stepsize_schedule) for _ in range(n_steps)]
-        table = self._fused_scalars_table(eps)
-        self.epsilon = eps[-1]
-        gen, cost, a = self.batch_generator, self.cost_fun, self.arena
-        pending, self._pending_window = getattr(self, "_pending_window", None), None
-        if pending is None:
-            first = []
-        else:                                     # a window next(sampler) drew one step ahead (base_classes._window_to_prefetch)
-            first = [int(pending[0])]
-        starts_host = np.concatenate([np.asarray(first, dtype=np.int32), gen.next_starts(n_steps - len(first))]) if first else gen.next_starts(n_steps)
-        starts = torch.as_tensor(starts_host, dtype=torch.int32).to(self.device)
+        eps = self._fused_stepsizes(n_steps)
+        starts = torch.as_tensor(self._fused_window_starts(n_steps)).to(self.device)
         costs = torch.empty(n_steps, dtype=self._torch_dtype, device=self.device)
-        if table is None:
-            self._fused_bnn_launch(starts, costs, eps[0], n_steps)
-        else:
-            self._fused_bnn_launch(starts, costs, eps[0], n_steps, scalars_steps=table)
-        self.n_iterations += n_steps
-        self._stats_valid = False                 # theta moved without the statistics workspace
-        self._grad_decay = float(cost.wdecay / ((a.n + 3e-16) * cost.n_examples))
-        self.cost = costs[-1]
+        self._fused_bnn_launch(starts, costs, eps[0], n_steps, scalars_steps=self._fused_scalars_table(eps))
+        self._fused_steps_done(n_steps, costs[-1])
         return costs

@@ -78,31 +78,22 @@ class FusedBNNChains(object):
         if any(s.n_iterations != first.n_iterations for s in self.samplers):
             raise ValueError("FusedBNNChains.steps: the chains are no longer at the same iteration "
                              "(a member was stepped on its own)")
-        eps = None
-        for s in self.samplers:
-            e = [next(s.stepsize_schedule) for _ in range(n_steps)]
-            if eps is not None and e != eps:
-                raise ValueError("FusedBNNChains.steps needs one stepsize sequence for all chains over the chunk")
-            eps = e
-            s.epsilon = eps[-1]
-        table = first._fused_scalars_table(eps)
-        gen, cost, a = first.batch_generator, first.cost_fun, first.arena
-        starts = np.stack([s.batch_generator.next_starts(n_steps) for s in self.samplers]).astype(np.int32)
+        eps = [s._fused_stepsizes(n_steps) for s in self.samplers]
+        if any(e != eps[0] for e in eps):
+            raise ValueError("FusedBNNChains.steps needs one stepsize sequence for all chains over the chunk")
+        starts = np.stack([s._fused_window_starts(n_steps) for s in self.samplers])
         starts = torch.as_tensor(starts).to(first.device).reshape(-1)
         costs = torch.empty(self.n_chains * n_steps, dtype=first._torch_dtype, device=first.device)
-        rows = [a.row(k) for k in first._FUSED_ROWS]
         # chain 0's rows are the bases; the kernel adds chain * chain_stride. Hand it views that span all chains.
+        a = first.arena
         span = (self.n_chains - 1) * self.chain_stride + a.n
-        bases = [torch.as_strided(self.storage, (span,), (1,), r.storage_offset() - self.storage.storage_offset())
-                 for r in rows]
-        first._fused_bnn_launch(starts, costs, eps[0], n_steps, n_chains=self.n_chains, chain_stride=self.chain_stride,
-                                bases=bases, **({} if table is None else {"scalars_steps": table}))
+        bases = [torch.as_strided(self.storage, (span,), (1,), a.row(k).storage_offset() - self.storage.storage_offset())
+                 for k in first._FUSED_ROWS]
+        first._fused_bnn_launch(starts, costs, eps[0][0], n_steps, n_chains=self.n_chains, chain_stride=self.chain_stride,
+                                bases=bases, scalars_steps=first._fused_scalars_table(eps[0]))
         costs = costs.view(self.n_chains, n_steps)
         for c, s in enumerate(self.samplers):
-            s.n_iterations += n_steps
-            s._stats_valid = False
-            s._grad_decay = float(cost.wdecay / ((a.n + 3e-16) * cost.n_examples))
-            s.cost = costs[c, -1]
+            s._fused_steps_done(n_steps, costs[c, -1])
         return costs
 
     def collect(self, n_samples, every=100):

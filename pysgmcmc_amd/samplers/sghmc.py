@@ -52,13 +52,3 @@ class SGHMCSampler(FusedBNNStepsMixin, BurnInMCMCSampler):
             eps, self.scale_grad, self.mdecay, self._adapting,
             xi=xi, stats=self._step_stats(), grad_decay=self._grad_decay, launch=self._launch(), opts=opts, **self._noise_args())
         self._stats_written()
-
-    # ------------------------------------------------------------------ fused small-model path (see _fused_bnn.py)
-    def _fused_bnn_launch(self, starts, costs, eps, n_steps, n_chains=1, chain_stride=None, bases=None, scalars_steps=None):
-        gen, cost, a = self.batch_generator, self.cost_fun, self.arena
-        rows = bases or [a.row(k) for k in self._FUSED_ROWS]
-        kernels.bnn_fused_sghmc_steps(
-            *rows, self._bnn_layer_sizes(), gen.x_dev, gen.y_dev.reshape(-1), starts, gen.batch_size,
-            cost.batch_size, cost.n_examples, cost.wdecay, cost.prior_mean, cost.prior_var,
-            eps, self.scale_grad, self.mdecay, self.n_iterations, n_steps, max(self.burn_in_steps, 0),
-            self._philox_seed, costs, n_chains=n_chains, chain_stride=chain_stride, scalars_steps=scalars_steps)

@@ -102,6 +102,24 @@ def test_whole_step_entries_refuse_null_arguments_before_any_launch():
     sizes = (ctypes.c_int * 4)(3, 7, 13, 1)
     d = ctypes.c_void_p(4096)
     net = (147, 148, 1, sizes, 3, d, d, 40, d, 5, 5.0, 40.0, 1.0, 1e-6, 0.01)
+    # a NULL theta: every one of the ten entries, through the argtypes _lib declares for it
+    table = {"steps": (1e-3,), "sched_steps": (d,)}
+    refused = 0
+    for sfx in ("f32", "f64"):
+        for kind, n_rows, other in (("sghmc", 7, (40.0, 0.05)), ("sgld", 6, (40.0, 1.0))):
+            for variant, first in table.items():
+                f = getattr(lib, "sgmcmc_bnn_fused_%s_%s_%s" % (kind, variant, sfx))
+                rc = f(None, *[d] * (n_rows - 1), *net, *first, *other, 0, 1, 0, 0, None, d, None)
+                assert rc == -1 and b"NULL argument" in lib.sgmcmc_last_error(), (kind, variant, sfx)
+                assert lib.sgmcmc_last_error().startswith(b"bnn_fused_%s_%s: " % (kind.encode(), variant.encode()))
+                refused += 1
+        f = getattr(lib, "sgmcmc_bnn_fused_rsghmc_steps_" + sfx)
+        assert f(None, d, d, *net, 1e-3, 1.0, 1.0, 1.0, 0.0, None, 0, 1, 0, None, d, None) == -1
+        assert lib.sgmcmc_last_error().startswith(b"bnn_fused_rsghmc_steps: NULL argument")
+        refused += 1
+    assert refused == 10
+    assert lib.sgmcmc_bnn_fused_sgld_steps_f32(None, d, d, d, d, d, *net, 1e-3, 40.0, 1.0, 0, 1, 0, 0, None, d, None) == -1
+    assert lib.sgmcmc_last_error().startswith(b"bnn_fused_sgld_steps")
     rc = lib.sgmcmc_bnn_fused_sghmc_sched_steps_f32(d, d, d, d, d, d, d, *net, None, 40.0, 0.05, 0, 1, 0, 0, None, d, None)
     assert rc == -1 and b"scalars_steps is NULL" in lib.sgmcmc_last_error()
     rc = lib.sgmcmc_bnn_fused_sgld_sched_steps_f64(d, d, d, d, d, d, *net, None, 40.0, 1.0, 0, 1, 0, 0, None, d, None)
@@ -113,3 +131,11 @@ def test_whole_step_entries_refuse_null_arguments_before_any_launch():
     assert rc == -1 and b"16-B aligned" in lib.sgmcmc_last_error()
     rc = lib.sgmcmc_bnn_fused_rsghmc_steps_f32(d, d, d, *net, 1e-3, 1.0, 1.0, 1.0, 0.0, None, 0, 1, 0, d, d, None)
     assert rc == -1 and b"n_params % 4 == 0" in lib.sgmcmc_last_error()
+
+
+def test_bnn_fused_steps_refuses_an_unknown_kind_before_touching_the_library(monkeypatch):
+    def no_library():
+        raise AssertionError("the library was asked for")
+    monkeypatch.setattr(kernels, "lib", no_library)
+    with pytest.raises(ValueError, match="kind must be one of rsghmc, sghmc, sgld"):
+        kernels.bnn_fused_steps("svgd", (), [1, 1], None, None, None, 1, 1.0, 1.0, 1.0, 1e-6, 0.01, (1e-3,), 0, 1, 0, 0, None)

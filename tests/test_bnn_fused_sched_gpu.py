@@ -6,7 +6,8 @@
   (this pins the table's derivation to the by-value one); chunking under the ramp is bit-exact;
 - the relativistic update phase is K3: theta', p' == ``kernels.rsghmc_step`` on the gradient row the step left;
 - relativistic whole steps track ``next(sampler)`` (GEMM path) and the float64 oracle trajectory;
-- many chains per launch, ``FusedBNNChains`` of relativistic samplers, shared ramps, disagreeing schedules;
+- many chains per launch, ``FusedBNNChains`` of relativistic samplers, shared ramps, disagreeing schedules, windows
+  the chains hold pending;
 - ``BayesianNeuralNetwork.train`` under the burn-in ramp takes the fused path;
 - the entry points' refusals."""
 import ctypes
@@ -382,6 +383,31 @@ def test_groups_refuse_mismatched_chains_and_disagreeing_schedules(gpu):
     sghmc = _chain(gpu, torch.float32, "sghmc", seed=61, init_seed=61, shared=ok[0].batch_generator)
     with pytest.raises(ValueError, match="does not fit"):
         FusedBNNChains([ok[0], sghmc])
+
+
+def _sghmc_pair(gpu, dt):
+    first = _chain(gpu, dt, "sghmc", seed=5, init_seed=5)
+    return [first, _chain(gpu, dt, "sghmc", seed=6, init_seed=6, shared=first.batch_generator)]
+
+
+@pytest.mark.parametrize("dt", DTS, ids=IDS)
+def test_group_takes_each_chains_pending_window_first(gpu, dt):
+    """A chain resumed from a ``state_dict`` with a ``pending_window`` (or stepped with ``next()`` under window prefetch)
+    holds a window its generator has already drawn. The group hands it to the kernel as that chain's first start, as
+    ``fused_bnn_steps`` does: same rows, same costs, nothing left pending, generators at the same place."""
+    grouped, twins = _sghmc_pair(gpu, dt), _sghmc_pair(gpu, dt)
+    for pair in (grouped, twins):
+        for s, start in zip(pair, (17, 63)):
+            s._pending_window = (start, False)
+    costs = FusedBNNChains(grouped).steps(5)
+    for c, (a, b) in enumerate(zip(grouped, twins)):
+        c1 = b.fused_bnn_steps(5)
+        for k in a._FUSED_ROWS:
+            assert torch.equal(a.arena.row(k), b.arena.row(k)), (c, k)
+        assert torch.equal(costs[c], c1) and torch.isfinite(c1).all(), c
+        assert a._pending_window is None and b._pending_window is None
+        assert int(a.batch_generator.next_starts(1)[0]) == int(b.batch_generator.next_starts(1)[0]), c
+        assert a.n_iterations == b.n_iterations == 5
 
 
 # ---- the user-visible hole ---------------------------------------------------------------------------------------------

@@ -62,7 +62,7 @@ def _n_params(sizes):
 
 
 def _lds_bytes(sizes, batch, esize):
-    """bnn_fused_steps' LDS formula: activations (act_off), deltas (del_off), the target window (lds_y), rounded up to
+    """bnn_fused_entry's LDS formula: activations (act_off), deltas (del_off), the target window (lds_y), rounded up to
     4 elements, then the parameter copy, after 160 B of reduction scratch."""
     elems = batch * sum(sizes) + batch * sum(sizes[1:]) + batch
     elems = (elems + 3) & ~3
