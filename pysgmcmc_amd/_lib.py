@@ -31,6 +31,7 @@ def build(force=False):
     deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip.h"))
     deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip_diag.h"))
     deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip_fused.h"))
+    deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip_fused_trace.h"))
     stale = (not os.path.exists(_LIB_PATH)
              or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(d) for d in deps))
     if force or stale:
@@ -42,6 +43,7 @@ _lib = None
 ABI_VERSION = 6               # SGMCMC_ABI_VERSION of include/sgmcmc_hip.h
 DIAG_ABI_VERSION = 1          # SGMCMC_DIAG_ABI_VERSION of include/sgmcmc_hip_diag.h (the diagnostics add-on)
 FUSED_ABI_VERSION = 1         # SGMCMC_FUSED_ABI_VERSION of include/sgmcmc_hip_fused.h (the whole-step add-on)
+FUSED_TRACE_ABI_VERSION = 1   # SGMCMC_FUSED_TRACE_ABI_VERSION of include/sgmcmc_hip_fused_trace.h (the thinned-trace add-on)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 
@@ -212,6 +214,15 @@ def _declare(lib):
                 f = getattr(lib, "sgmcmc_bnn_fused_%s_sched_steps_%s" % (kind, sfx))
                 f.argtypes = [_vp] * n_rows + net + [_vp] + [real] * (n_scalars - 1) + tail
                 f.restype = _ci
+    # include/sgmcmc_hip_fused_trace.h: kind, host array of rows, the net run, host array of scalars, table, first_step,
+    # n_steps, burn_in_steps, seed_base, xi, cost_out, trace, its chain stride, capacity, row, every, phase, stream
+    lib.sgmcmc_fused_trace_abi_version.restype = _ci
+    for sfx, real in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        f = getattr(lib, "sgmcmc_bnn_fused_trace_steps_" + sfx)
+        f.argtypes = ([_ci, ctypes.POINTER(_vp), _ci] + net + [ctypes.POINTER(real), _ci, _vp] + [_u64] * 4
+                      + [_vp, _vp, _vp, _sz] + [_u64] * 4 + [_vp])
+        f.restype = _ci
+
 
 def lib():
     """The loaded library (argtypes declared). Raises SgmcmcLibraryError if absent."""
@@ -233,6 +244,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: diagnostics ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_fused_abi_version() != FUSED_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: whole-step add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_fused_trace_abi_version() != FUSED_TRACE_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: thinned-trace add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

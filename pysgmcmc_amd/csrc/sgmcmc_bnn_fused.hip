@@ -31,13 +31,19 @@
 // arrive by value (bnn_fused_sghmc_kernel<T, KIND>: one stepsize for the launch) or from a device table of one block per step
 // (bnn_fused_sghmc_kernel<T, KIND + FUSED_TABLE>: a stepsize schedule inside the launch; include/sgmcmc_hip_fused.h). The
 // table is a template parameter, so the by-value kernels carry no trace of it.
+//
+// Thinned device trace (KIND + FUSED_TRACE, include/sgmcmc_hip_fused_trace.h): after every `trace_every`-th step the workgroup
+// copies theta' from its LDS copy into the next row of a device matrix, so a run that keeps samples needs no launch boundary
+// and no host copy per kept sample. A template parameter again: the untraced kernels are the instruction streams they were.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <utility>
 
 #include "sgmcmc_hip.h"
 #include "sgmcmc_hip_fused.h"
+#include "sgmcmc_hip_fused_trace.h"
 
 #pragma clang fp contract(off)
 
@@ -51,6 +57,7 @@ namespace {
 
 constexpr int FUSED_MAX_LAYERS = 8;
 constexpr int FUSED_TABLE = 4;             // bit of the kernel's KIND_ parameter: per-step scalars table
+constexpr int FUSED_TRACE = 8;             // bit of the kernel's KIND_ parameter: every trace_every-th theta' into a device trace
 constexpr int FUSED_THREADS = 512;       // 8 waves: 2 per SIMD, 256 registers each (1024 lanes spilled registers: 24.3 vs 20.4 us per step)
 
 __device__ __forceinline__ float tanh_t(float x) { return tanhf(x); }
@@ -92,6 +99,11 @@ struct FusedArgs {
     T rs_eps, rs_mass, rs_D, rs_m2c2, rs_nscale, rs_inv; // host-derived scalars of K3 (relativistic chains); rs_inv = 1 / m2c2
     int rs_pow2;                                         // m2c2 is a power of two: RsghmcOp's POW2 form (by-value launches only)
     const T *scalars_steps;                              // table kernels: [n_steps][5], the operator's scalars_dev block of step t
+    // trace kernels: local step t is kept iff (trace_phase + t + 1) % trace_every == 0; the j-th kept step of the launch writes
+    // theta' to trace + chain * trace_chain_stride + (trace_row + j) * n_params
+    T *trace;
+    size_t trace_chain_stride;
+    uint64_t trace_row, trace_every, trace_phase;
 };
 
 // block-wide sum of one double per lane; every lane returns the total. red: 17 doubles of LDS.
@@ -186,11 +198,13 @@ __device__ __forceinline__ double update_phase_rsghmc(const FusedArgs<T> &a, T *
 // KIND_: the update operator (0 SGHMC, 1 SGLD, 2 relativistic SGHMC), + FUSED_TABLE when the operator's scalars come from
 // FusedArgs::scalars_steps (row t at step t: a stepsize schedule inside the launch) instead of by value. A template
 // parameter, not a branch: bnn_fused_sghmc_kernel<T, 0> and <T, 1> are the by-value kernels they always were.
+// + FUSED_TRACE: the kept steps' theta' go to FusedArgs::trace as well.
 template <typename T, int KIND_>
 __global__ void __launch_bounds__(FUSED_THREADS) bnn_fused_sghmc_kernel(const FusedArgs<T> a)
 {
     constexpr int KIND = KIND_ & 3;
     constexpr bool TABLE = (KIND_ & FUSED_TABLE) != 0;
+    constexpr bool TRACE = (KIND_ & FUSED_TRACE) != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     double *red = reinterpret_cast<double *>(smem_raw);           // 17 doubles (+ pad to 160 B)
     T *lds = reinterpret_cast<T *>(smem_raw + 160);
@@ -221,6 +235,9 @@ __global__ void __launch_bounds__(FUSED_THREADS) bnn_fused_sghmc_kernel(const Fu
         if (tid < B) y_next = a.y[st + tid];
     };
     if (prefetch) fetch_window(0);
+    // steps left until the next kept one (a countdown instead of a 64-bit remainder per step), and where its row goes
+    uint64_t keep_in = TRACE ? a.trace_every - a.trace_phase : 0;
+    T *trow = TRACE ? a.trace + (size_t)chain * a.trace_chain_stride + (size_t)a.trace_row * a.n_params : nullptr;
     for (uint64_t t = 0; t < a.n_steps; ++t) {
         const uint64_t step = a.first_step + t;
         // ---- parameters into LDS (first step of the launch: later ones find theta' there, written by the update phase);
@@ -400,13 +417,23 @@ __global__ void __launch_bounds__(FUSED_THREADS) bnn_fused_sghmc_kernel(const Fu
         }
         __threadfence_block();
         tsq = block_sum(share, red);                      // barriers inside: the new theta is visible to the block
+        if constexpr (TRACE) {
+            // wl holds theta' (the bits the update stored to the arena) and is not written again before the next update,
+            // many barriers away: plain element stores, coalesced over the lanes, no alignment demand on a row (n_params is odd
+            // for many nets)
+            if (--keep_in == 0) {
+                for (size_t i = tid; i < a.n_params; i += nt) trow[i] = wl[i];
+                trow += a.n_params;
+                keep_in = a.trace_every;
+            }
+        }
     }
 }
 
-template <typename T, int KIND, bool TABLE>
+template <typename T, int KIND, bool TABLE, bool TRACE>
 int launch_fused(const FusedArgs<T> &a, int n_chains, size_t lds_bytes, hipStream_t st)
 {
-    auto kernel = &bnn_fused_sghmc_kernel<T, KIND | (TABLE ? FUSED_TABLE : 0)>;
+    auto kernel = &bnn_fused_sghmc_kernel<T, KIND | (TABLE ? FUSED_TABLE : 0) | (TRACE ? FUSED_TRACE : 0)>;
     if (lds_bytes > 64 * 1024) {
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)lds_bytes);
@@ -441,15 +468,25 @@ constexpr const char *FUSED_NAME[3][2] = {{"bnn_fused_sghmc_steps", "bnn_fused_s
                                           {"bnn_fused_sgld_steps", "bnn_fused_sgld_sched_steps"},
                                           {"bnn_fused_rsghmc_steps", "bnn_fused_rsghmc_steps"}};
 
+// Where a traced launch keeps its samples (include/sgmcmc_hip_fused_trace.h)
+template <typename T>
+struct FusedTrace {
+    T *trace;
+    size_t chain_stride;
+    uint64_t capacity, row, every, phase;
+};
+
 // The one host path from every entry point to the launch. `by_value`: the scalars the operator's five by-value scalars are
 // derived from (sgmcmc_scalars.hpp). `scalars_steps`: DEVICE table [n_steps][5] that replaces those five step by step, or
-// NULL; `need_table`: the entry point has no by-value stepsize, so NULL is an error and `by_value` is not read.
+// NULL; `need_table`: the entry point has no by-value stepsize, so NULL is an error and `by_value` is not read. `trace`: NULL, or
+// the thinned device trace of the launch, checked after everything else under the name `what_traced`.
 template <typename T, int KIND>
 int bnn_fused_entry(T *const (&rows)[FUSED_N_ROWS[KIND]], const FusedNet<T> &n, const T (&by_value)[FUSED_N_SCALARS[KIND]],
                     const T *scalars_steps, bool need_table, uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps,
-                    uint64_t seed_base, const T *xi, T *cost_out, sgmcmc_stream_t stream)
+                    uint64_t seed_base, const T *xi, T *cost_out, sgmcmc_stream_t stream, const FusedTrace<T> *trace = nullptr,
+                    const char *what_traced = nullptr)
 {
-    const char *what = FUSED_NAME[KIND][need_table];
+    const char *what = trace ? what_traced : FUSED_NAME[KIND][need_table];
     if (n_steps == 0 || n.n_chains == 0) return 0;
     bool null_row = false;
     for (T *p : rows) null_row |= !p;
@@ -515,8 +552,57 @@ int bnn_fused_entry(T *const (&rows)[FUSED_N_ROWS[KIND]], const FusedNet<T> &n, 
     a.first_step = first_step; a.n_steps = n_steps; a.burn_in_steps = burn_in_steps; a.seed_base = seed_base;
     a.xi = xi; a.cost_out = cost_out; a.scalars_steps = scalars_steps;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return scalars_steps ? launch_fused<T, KIND, true>(a, n.n_chains, lds_bytes, st)
-                         : launch_fused<T, KIND, false>(a, n.n_chains, lds_bytes, st);
+    if (trace) {
+        typedef unsigned __int128 u128;                    // the bounds below must not wrap, whatever the caller passed
+        if (!trace->trace) return fail(SGMCMC_EINVAL, "%s: trace is NULL", what);
+        if (trace->every == 0) return fail(SGMCMC_EINVAL, "%s: trace_every must be >= 1", what);
+        if (trace->phase >= trace->every) return fail(SGMCMC_EINVAL, "%s: trace_phase must be < trace_every", what);
+        if ((u128)trace->row + ((u128)trace->phase + n_steps) / trace->every > (u128)trace->capacity)
+            return fail(SGMCMC_EINVAL, "%s: the launch keeps more rows than trace_capacity holds from trace_row on", what);
+        if (n.n_chains > 1 && (u128)trace->chain_stride < (u128)trace->capacity * n.n_params)
+            return fail(SGMCMC_EINVAL, "%s: trace_chain_stride must be >= trace_capacity * n_params", what);
+        a.trace = trace->trace; a.trace_chain_stride = trace->chain_stride;
+        a.trace_row = trace->row; a.trace_every = trace->every; a.trace_phase = trace->phase;
+        return scalars_steps ? launch_fused<T, KIND, true, true>(a, n.n_chains, lds_bytes, st)
+                             : launch_fused<T, KIND, false, true>(a, n.n_chains, lds_bytes, st);
+    }
+    return scalars_steps ? launch_fused<T, KIND, true, false>(a, n.n_chains, lds_bytes, st)
+                         : launch_fused<T, KIND, false, false>(a, n.n_chains, lds_bytes, st);
+}
+
+// include/sgmcmc_hip_fused_trace.h: the kind, its rows and its by-value scalars arrive as values, so ONE entry per dtype reaches
+// the three instantiations of the host path above. A table replaces the by-value stepsize as in the `sched` entries.
+template <typename T, int KIND, size_t... R, size_t... S>
+int bnn_fused_trace_kind(std::index_sequence<R...>, std::index_sequence<S...>, T *const *rows, const FusedNet<T> &n,
+                         const T *scalars, const T *scalars_steps, uint64_t first_step, uint64_t n_steps,
+                         uint64_t burn_in_steps, uint64_t seed_base, const T *xi, T *cost_out, const FusedTrace<T> &tr,
+                         sgmcmc_stream_t stream)
+{
+    // SGLD's entry takes eps, scale_grad, A; its operator's derivation eps, A, scale_grad
+    constexpr size_t order[3][5] = {{0, 1, 2, 0, 0}, {0, 2, 1, 0, 0}, {0, 1, 2, 3, 4}};
+    return bnn_fused_entry<T, KIND>({rows[R]...}, n, {scalars[order[KIND][S]]...}, scalars_steps,
+                                    KIND != 2 && scalars_steps != nullptr, first_step, n_steps, KIND == 2 ? 0 : burn_in_steps,
+                                    seed_base, xi, cost_out, stream, &tr, "bnn_fused_trace_steps");
+}
+
+template <typename T>
+int bnn_fused_trace_entry(int kind, T *const *rows, int n_rows, const FusedNet<T> &n, const T *scalars, int n_scalars,
+                          const T *scalars_steps, uint64_t first_step, uint64_t n_steps, uint64_t burn_in_steps,
+                          uint64_t seed_base, const T *xi, T *cost_out, const FusedTrace<T> &tr, sgmcmc_stream_t stream)
+{
+    const char *what = "bnn_fused_trace_steps";
+    if (n_steps == 0 || n.n_chains == 0) return 0;
+    if (kind < 0 || kind > 2) return fail(SGMCMC_EINVAL, "%s: kind must be 0 (SGHMC), 1 (SGLD) or 2 (relativistic), not %d", what, kind);
+    if (n_rows != FUSED_N_ROWS[kind]) return fail(SGMCMC_EINVAL, "%s: kind %d has %d rows, not %d", what, kind, FUSED_N_ROWS[kind], n_rows);
+    if (n_scalars != FUSED_N_SCALARS[kind])
+        return fail(SGMCMC_EINVAL, "%s: kind %d has %d scalars, not %d", what, kind, FUSED_N_SCALARS[kind], n_scalars);
+    if (!rows || !scalars) return fail(SGMCMC_EINVAL, "%s: NULL argument", what);
+#define TRACE_KIND(K)                                                                                                      \
+    bnn_fused_trace_kind<T, K>(std::make_index_sequence<FUSED_N_ROWS[K]>{}, std::make_index_sequence<FUSED_N_SCALARS[K]>{},  \
+                               rows, n, scalars, scalars_steps, first_step, n_steps, burn_in_steps, seed_base, xi, cost_out, \
+                               tr, stream)
+    return kind == 0 ? TRACE_KIND(0) : kind == 1 ? TRACE_KIND(1) : TRACE_KIND(2);
+#undef TRACE_KIND
 }
 
 // HOST table [n_steps][5] of an operator's scalars for the stepsizes eps[0 .. n_steps): `derive(eps, row)` is the shared derivation
@@ -638,6 +724,25 @@ FUSED_TWINS
     {                                                                                                                      \
         return bnn_fused_entry<T, 2>({theta, p, grad}, FUSED_NET_PACK(T), {eps, mass, c, D, b_hat}, scalars_steps, false,  \
                                      first_step, n_steps, 0, seed_base, xi, cost_out, stream);                             \
+    }
+FUSED_TWINS
+#undef ENTRY
+
+// ---- include/sgmcmc_hip_fused_trace.h
+
+int sgmcmc_fused_trace_abi_version(void) { return SGMCMC_FUSED_TRACE_ABI_VERSION; }
+
+#define ENTRY(SFX, T)                                                                                                      \
+    int sgmcmc_bnn_fused_trace_steps_##SFX(int kind, T *const *rows, int n_rows, FUSED_NET_PARAMS(T) const T *scalars,     \
+                                           int n_scalars, const T *scalars_steps, uint64_t first_step, uint64_t n_steps,   \
+                                           uint64_t burn_in_steps, uint64_t seed_base, const T *xi, T *cost_out, T *trace, \
+                                           size_t trace_chain_stride, uint64_t trace_capacity, uint64_t trace_row,         \
+                                           uint64_t trace_every, uint64_t trace_phase, sgmcmc_stream_t stream)             \
+    {                                                                                                                      \
+        return bnn_fused_trace_entry<T>(kind, rows, n_rows, FUSED_NET_PACK(T), scalars, n_scalars, scalars_steps,          \
+                                        first_step, n_steps, burn_in_steps, seed_base, xi, cost_out,                       \
+                                        FusedTrace<T>{trace, trace_chain_stride, trace_capacity, trace_row, trace_every,   \
+                                                      trace_phase}, stream);                                               \
     }
 FUSED_TWINS
 #undef ENTRY

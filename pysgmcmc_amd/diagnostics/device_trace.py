@@ -5,7 +5,9 @@ per parameter dimension from traces that are Python lists of host arrays; ``samp
 its estimator for ONE scalar (an FFT and a host read per call). Here the trace never leaves the device:
 
   ``DeviceTrace``                 a preallocated ``(capacity, n_params)`` matrix; ``append`` is one stream-ordered
-                                  device copy, ``record`` steps a sampler and keeps its flat ``theta`` row
+                                  device copy, ``record`` steps a sampler and keeps its flat ``theta`` row; with
+                                  ``fused=True`` the whole-step BNN kernel K8 writes the kept rows itself, in ONE launch
+                                  (``sampler.fused_bnn_steps(n, trace, keep_every)``)
   ``effective_n_all``             one launch of K10 (``kernels.ess_variogram``) -> int64 ESS of all P parameters, on the
                                   device, no host synchronisation
   ``effective_sample_sizes_of``   the reference's ``{name: array shaped like the parameter}`` cut from that vector
@@ -32,6 +34,9 @@ class DeviceTrace(object):
             raise ValueError("DeviceTrace: n_params and capacity must be >= 0")
         self.buffer = torch.empty(self.capacity, self.n_params, dtype=dtype, device=device)
         self._len = 0
+        # steps a whole-step launch (``fused_bnn_steps(n, trace, keep_every)``) took after the last sample it kept: the next
+        # chunk continues the thinning from here
+        self.steps_since_kept = 0
         # set by record(): how to cut a flat vector into the sampler's parameters
         self.param_names = None
         self.param_shapes = None
@@ -63,22 +68,57 @@ class DeviceTrace(object):
 
     def reset(self):
         self._len = 0
+        self.steps_since_kept = 0
+
+    def describe(self, sampler):
+        """Take the names, shapes and offsets of ``sampler``'s parameters (what ``effective_sample_sizes_of`` cuts by)."""
+        arena = sampler.arena
+        self.param_names = list(getattr(sampler, "param_names", [str(i) for i in range(len(arena.shapes))]))
+        self.param_shapes = list(arena.shapes)
+        self.param_offsets = list(arena.offsets)
+
+    def kept_rows(self, n_steps, keep_every):
+        """How many of the next ``n_steps`` steps a run that keeps every ``keep_every``-th one would keep, counted from
+        the last kept sample."""
+        return (self.steps_since_kept + int(n_steps)) // int(keep_every)
+
+    def advance(self, n_steps, keep_every):
+        """Account for ``n_steps`` steps whose every ``keep_every``-th sample something else wrote into the next rows of
+        ``buffer`` (a whole-step launch): the length grows by the kept count, which is returned, and
+        ``steps_since_kept`` moves on. ``IndexError`` if the rows do not exist."""
+        n_steps, keep_every = int(n_steps), int(keep_every)
+        if n_steps < 0 or keep_every < 1:
+            raise ValueError("DeviceTrace.advance: n_steps must be >= 0 and keep_every >= 1")
+        kept = self.kept_rows(n_steps, keep_every)
+        if self._len + kept > self.capacity:
+            raise IndexError("DeviceTrace: capacity of %d samples exhausted" % self.capacity)
+        self._len += kept
+        self.steps_since_kept = (self.steps_since_kept + n_steps) % keep_every
+        return kept
 
     @classmethod
-    def record(cls, sampler, n_samples, keep_every=1):
+    def record(cls, sampler, n_samples, keep_every=1, fused=False):
         """Step ``sampler`` ``n_samples * keep_every`` times and keep ``sampler.arena.row("theta")`` after every
         ``keep_every``-th step. The sampler's ``sample_format`` is ``"view"`` for the duration (no per-step host
         copy) and restored afterwards, also when a step raises. The chain itself is untouched: the appends only read
-        theta, in stream order after the step that produced it."""
+        theta, in stream order after the step that produced it.
+
+        ``fused=True``: the same samples of a chain that fits the whole-step BNN kernel
+        (``sampler.fused_bnn_available()``, else ``ValueError``) in ONE launch that writes the kept rows itself:
+        ``sampler.fused_bnn_steps(n_samples * keep_every, trace, keep_every)``."""
         n_samples, keep_every = int(n_samples), int(keep_every)
         if n_samples < 0 or keep_every < 1:
             raise ValueError("DeviceTrace.record: n_samples must be >= 0 and keep_every >= 1")
+        if fused and not (hasattr(sampler, "fused_bnn_available") and sampler.fused_bnn_available()):
+            raise ValueError("DeviceTrace.record: fused=True needs a sampler whose fused_bnn_available() is true")
         arena = sampler.arena
         theta = arena.row("theta")
         trace = cls(theta.numel(), n_samples, theta.device, theta.dtype)
-        trace.param_names = list(getattr(sampler, "param_names", [str(i) for i in range(len(arena.shapes))]))
-        trace.param_shapes = list(arena.shapes)
-        trace.param_offsets = list(arena.offsets)
+        trace.describe(sampler)
+        if fused:
+            if n_samples:
+                sampler.fused_bnn_steps(n_samples * keep_every, trace, keep_every)
+            return trace
         fmt = sampler.sample_format
         sampler.sample_format = "view"
         try:

@@ -543,20 +543,29 @@ def step_scalars_table(kind, eps_list, *scalars, dtype, device):
 # kind -> (where the C entry's scalars after eps stand in the sampler's ``scalars``; a burn-in sampler's entry, which has a
 # ``burn_in_steps`` argument and a ``sched`` twin for a table, where the relativistic entry takes the table as an option)
 _FUSED_KINDS = {"sghmc": ((1, 2), True), "sgld": ((2, 1), True), "rsghmc": ((1, 2, 3, 4), False)}
+_FUSED_KIND_INDEX = {"sghmc": 0, "sgld": 1, "rsghmc": 2}      # `kind` of sgmcmc_bnn_fused_trace_steps_*
 
 
 def bnn_fused_steps(kind, rows, layer_sizes, X, y, window_starts, batch, batch_size, n_examples, wdecay, prior_mean,
                     prior_var, scalars, first_step, n_steps, burn_in_steps, seed_base, cost_out, xi=None, n_chains=1,
-                    chain_stride=None, scalars_steps=None):
+                    chain_stride=None, scalars_steps=None, trace=None, trace_every=1, trace_row=0, trace_phase=0):
     """``n_steps`` complete steps of a small tanh-MLP BNN per chain in one launch, whichever the update: ``kind`` "sghmc",
     "sgld" or "rsghmc", ``rows`` the kind's state rows in the entry's order, ``scalars`` the sampler's scalars in the order
     of ``step_scalars`` (``eps`` first). ``scalars_steps`` (``step_scalars_table(kind, ...)``) replaces ``eps`` step by
-    step; ``burn_in_steps`` is ignored for "rsghmc". The one caller of ``sgmcmc_bnn_fused_*_steps_*``."""
+    step; ``burn_in_steps`` is ignored for "rsghmc". The one caller of ``sgmcmc_bnn_fused_*_steps_*``.
+
+    ``trace``: a contiguous device tensor ``(capacity, n_params)`` (one chain) or ``(n_chains, capacity, n_params)`` of
+    the step's dtype. The launch then keeps theta after every ``trace_every``-th step in it, from row ``trace_row`` on
+    (``sgmcmc_bnn_fused_trace_steps_*``, include/sgmcmc_hip_fused_trace.h): step ``t`` of the launch is kept iff
+    ``(trace_phase + t + 1) % trace_every == 0``, where ``trace_phase < trace_every`` counts the steps taken since the
+    last kept one. The chain and its costs are those of the untraced launch, bit for bit."""
     import ctypes
     if kind not in _FUSED_KINDS:
         raise ValueError("bnn_fused_steps: kind must be one of %s, not %r" % (", ".join(sorted(_FUSED_KINDS)), kind))
     order, burn_in = _FUSED_KINDS[kind]
     theta, sched = rows[0], burn_in and scalars_steps is not None
+    if trace is not None:
+        _fused_trace_check(trace, theta, layer_sizes, n_chains, trace_every, trace_row, trace_phase)
     name = "sgmcmc_bnn_fused_%s_%ssteps" % (kind, "sched_" if sched else "")
     f = getattr(lib(), "%s_%s" % (name, _sfx(theta)))
     sizes = [int(v) for v in layer_sizes]
@@ -568,6 +577,11 @@ def bnn_fused_steps(kind, rows, layer_sizes, X, y, window_starts, batch, batch_s
     if scalars_steps is not None and (scalars_steps.dtype != theta.dtype or scalars_steps.numel() != 5 * int(n_steps)):
         raise TypeError("scalars_steps must hold n_steps x 5 elements of the step's dtype (kernels.step_scalars_table)")
     other = [float(scalars[i]) for i in order]
+    if trace is not None:
+        return _bnn_fused_trace_steps(kind, rows, sizes, n_params, X, y, window_starts, batch, batch_size, n_examples, wdecay,
+                                      prior_mean, prior_var, [float(scalars[0])] + other, first_step, n_steps, burn_in_steps,
+                                      seed_base, cost_out, xi, n_chains, chain_stride, scalars_steps, trace, trace_every,
+                                      trace_row, trace_phase)
     by_value = [_ptr(scalars_steps)] + other if sched else [float(scalars[0])] + other
     with _on(theta):
         rc = f(*[_ptr(r) for r in rows], n_params, int(chain_stride), int(n_chains), (ctypes.c_int * len(sizes))(*sizes),
@@ -576,6 +590,44 @@ def bnn_fused_steps(kind, rows, layer_sizes, X, y, window_starts, batch, batch_s
                *([] if burn_in else [_ptr(scalars_steps)]), int(first_step), int(n_steps),
                *([int(burn_in_steps)] if burn_in else []), int(seed_base), _ptr(xi), _ptr(cost_out), _stream(theta))
     check(rc, name)
+    return cost_out
+
+
+def _fused_trace_check(trace, theta, layer_sizes, n_chains, trace_every, trace_row, trace_phase):
+    """The Python-side refusals of a traced ``bnn_fused_steps``, before the library is reached."""
+    sizes = [int(v) for v in layer_sizes]
+    n_params = sum(sizes[l] * sizes[l + 1] + sizes[l + 1] for l in range(len(sizes) - 1)) + 1
+    if not torch.is_tensor(trace) or trace.dtype != theta.dtype:
+        raise TypeError("trace must be a device tensor of the step's dtype (%s)" % theta.dtype)
+    if trace.device != theta.device:
+        raise TypeError("trace lives on %s, the chain on %s" % (trace.device, theta.device))
+    if not trace.is_contiguous() or not (
+            (trace.dim() == 2 and n_chains == 1 and trace.shape[1] == n_params)
+            or (trace.dim() == 3 and trace.shape[0] == n_chains and trace.shape[2] == n_params)):
+        raise TypeError("trace must be a contiguous (capacity, %d) tensor for one chain or (%d, capacity, %d) for the "
+                        "launch's chains, got %s" % (n_params, n_chains, n_params, tuple(trace.shape)))
+    if int(trace_every) < 1 or not 0 <= int(trace_phase) < int(trace_every) or int(trace_row) < 0:
+        raise ValueError("trace_every must be >= 1, 0 <= trace_phase < trace_every and trace_row >= 0")
+
+
+def _bnn_fused_trace_steps(kind, rows, sizes, n_params, X, y, window_starts, batch, batch_size, n_examples, wdecay, prior_mean,
+                           prior_var, entry_scalars, first_step, n_steps, burn_in_steps, seed_base, cost_out, xi, n_chains,
+                           chain_stride, scalars_steps, trace, trace_every, trace_row, trace_phase):
+    """The traced launch of ``bnn_fused_steps``; ``entry_scalars``: the kind's scalars in the order of its C entry."""
+    import ctypes
+    theta = rows[0]
+    capacity = int(trace.shape[-2])
+    real = ctypes.c_float if theta.dtype == torch.float32 else ctypes.c_double
+    f = getattr(lib(), "sgmcmc_bnn_fused_trace_steps_" + _sfx(theta))
+    with _on(theta):
+        rc = f(_FUSED_KIND_INDEX[kind], (ctypes.c_void_p * len(rows))(*[_ptr(r) for r in rows]), len(rows), n_params,
+               int(chain_stride), int(n_chains), (ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, _ptr(X), _ptr(y),
+               int(X.shape[0]), _ptr(window_starts), int(batch), float(batch_size), float(n_examples), float(wdecay),
+               float(prior_mean), float(prior_var), (real * len(entry_scalars))(*entry_scalars), len(entry_scalars),
+               _ptr(scalars_steps), int(first_step), int(n_steps), int(burn_in_steps), int(seed_base), _ptr(xi),
+               _ptr(cost_out), _ptr(trace), capacity * n_params, capacity, int(trace_row), int(trace_every),
+               int(trace_phase), _stream(theta))
+    check(rc, "sgmcmc_bnn_fused_trace_steps")
     return cost_out
 
 

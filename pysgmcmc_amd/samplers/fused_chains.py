@@ -69,12 +69,20 @@ class FusedBNNChains(object):
         return torch.as_strided(self.storage, (self.n_chains, a.n), (self.chain_stride, 1),
                                 a.row("theta").storage_offset() - self.storage.storage_offset())
 
-    def steps(self, n_steps):
+    def steps(self, n_steps, trace=None, keep_every=1, trace_row=0, trace_phase=0):
         """Advance every chain by ``n_steps`` steps in one launch; returns the ``[n_chains, n_steps]`` costs
         (cost at the parameters before each step). The stepsize may move inside the chunk when every chain's schedule
-        yields the same ``n_steps`` values (one shared table of per-step scalars); chains whose schedules disagree raise."""
+        yields the same ``n_steps`` values (one shared table of per-step scalars); chains whose schedules disagree raise.
+
+        ``trace``: a contiguous ``(n_chains, capacity, n_params)`` device tensor of the chains' dtype. The launch keeps
+        every chain's theta after each step ``t`` (0-based) with ``(trace_phase + t + 1) % keep_every == 0`` in its slab,
+        from row ``trace_row`` on (``kernels.bnn_fused_steps``); the chains and the costs are those of the untraced call."""
         n_steps = int(n_steps)
         first = self.samplers[0]
+        traced = {} if trace is None else dict(trace=trace, trace_every=keep_every, trace_row=trace_row,
+                                               trace_phase=trace_phase)
+        if trace is not None and not (torch.is_tensor(trace) and trace.dim() == 3):
+            raise TypeError("FusedBNNChains.steps: trace must be an (n_chains, capacity, n_params) device tensor")
         if any(s.n_iterations != first.n_iterations for s in self.samplers):
             raise ValueError("FusedBNNChains.steps: the chains are no longer at the same iteration "
                              "(a member was stepped on its own)")
@@ -90,21 +98,22 @@ class FusedBNNChains(object):
         bases = [torch.as_strided(self.storage, (span,), (1,), a.row(k).storage_offset() - self.storage.storage_offset())
                  for k in first._FUSED_ROWS]
         first._fused_bnn_launch(starts, costs, eps[0][0], n_steps, n_chains=self.n_chains, chain_stride=self.chain_stride,
-                                bases=bases, scalars_steps=first._fused_scalars_table(eps[0]))
+                                bases=bases, scalars_steps=first._fused_scalars_table(eps[0]), **traced)
         costs = costs.view(self.n_chains, n_steps)
         for c, s in enumerate(self.samplers):
             s._fused_steps_done(n_steps, costs[c, -1])
         return costs
 
     def collect(self, n_samples, every=100):
-        """``n_samples`` thinned snapshots of all chains: a ``[n_chains, n_samples, n_params]`` device tensor (one
-        launch of ``every`` steps per snapshot), ready for
+        """``n_samples`` thinned snapshots of all chains: a ``[n_chains, n_samples, n_params]`` device tensor, written
+        by ONE launch of ``n_samples * every`` steps that keeps every ``every``-th theta itself (no launch boundary and no
+        copy per snapshot), ready for ``diagnostics.device_trace.effective_n_all`` and
         ``diagnostics.sampler_diagnostics.gelman_rubin_from_chains`` / ``effective_n``."""
+        n_samples, every = int(n_samples), int(every)
         a = self.samplers[0].arena
-        out = torch.empty(self.n_chains, int(n_samples), a.n, dtype=self.storage.dtype, device=self.storage.device)
-        for k in range(int(n_samples)):
-            self.steps(every)
-            out[:, k].copy_(self.theta())
+        out = torch.empty(self.n_chains, n_samples, a.n, dtype=self.storage.dtype, device=self.storage.device)
+        if n_samples > 0:
+            self.steps(n_samples * every, trace=out, keep_every=every)
         return out
 
     @classmethod
