@@ -190,14 +190,21 @@ def weight_prior_log_like(parameters, wdecay=1.0, dtype=torch.float64):
 # ------------------------------------------------------------------ cost path
 
 class _CostPlan(object):
-    """The launch sequence one configuration of the MLP cost path runs (built by ``BNNCost._plan``, walked by every step)."""
-    __slots__ = ("forward", "head", "backward", "ones_row", "x_ones", "single_out", "gw_batch", "gw_planes", "fresh")
+    """The launch sequence one configuration of the MLP cost path runs (built by ``BNNCost._plan``, walked by every step), and
+    the scratch buffers its launches write: ``dot_parts``, ``colsum_parts`` (a pair, used in turns), ``planes_h`` / ``planes_d``
+    (``None`` where the plan has no launch that needs them). The walk takes scratch from the plan only. The tensors come from the
+    workspace's grow-only pool (``BNNCost._scratch``): plans with the same need share them, and none is replaced or freed while
+    the workspace lives -- a hipGraph captured from this plan's walk keeps valid addresses whatever plans are built after it."""
+    __slots__ = ("forward", "head", "backward", "ones_row", "x_ones", "single_out", "gw_batch", "gw_planes", "fresh",
+                 "dot_parts", "colsum_parts", "planes_h", "planes_d")
 
-    def __init__(self, forward, head, backward, ones_row, x_ones, single_out, gw_batch=None, gw_planes=False):
+    def __init__(self, forward, head, backward, ones_row, x_ones, single_out, gw_batch=None, gw_planes=False,
+                 dot_parts=None, colsum_parts=None, planes_h=None, planes_d=None):
         self.forward, self.head, self.backward = tuple(forward), head, dict(backward)
         self.ones_row, self.x_ones, self.single_out, self.gw_batch = ones_row, x_ones, single_out, gw_batch
         self.gw_planes = bool(gw_planes)                          # the batched weight gradients on the bf16 matrix pipe (3 exact planes)
         self.fresh = True                                         # not evaluated yet (BNNCost.auto_gemm_tuning acts on the first evaluation)
+        self.dot_parts, self.colsum_parts, self.planes_h, self.planes_d = dot_parts, colsum_parts, planes_h, planes_d
 
     def as_dict(self):
         d = {"forward": list(self.forward), "head": self.head, "backward": dict(self.backward),
@@ -207,6 +214,92 @@ class _CostPlan(object):
             d["batched_weight_gradient_arithmetic"] = ("3 exact bf16 planes per operand, 6 bf16 MFMA products, fp32 accumulation"
                                                        if self.gw_planes else "library fp32 product")
         return d
+
+
+def _stride_of(ts):
+    """Elements between consecutive tensors of ``ts`` if they are contiguous, equally spaced views of ONE allocation, else None."""
+    base = ts[0].untyped_storage().data_ptr()
+    if not all(t.is_contiguous() and t.untyped_storage().data_ptr() == base for t in ts):
+        return None                                               # (one strided view must be able to span them: one allocation)
+    gaps = {ts[k + 1].data_ptr() - ts[k].data_ptr() for k in range(len(ts) - 1)}
+    gap = gaps.pop() if len(gaps) == 1 else 0
+    return gap // ts[0].element_size() if gap > 0 and gap % ts[0].element_size() == 0 else None
+
+
+# The five decisions of BNNCost._plan (its docstring names the op strings). They look at shapes and addresses and allocate nothing.
+# `pays(rows, cols)`: the fused launch of a rows x cols output is worth taking; `fused_head`: loss head + last layer's backward in one launch.
+
+def _plan_forward(params, X, hs, fused_layers, pays, single_out, fused_head):
+    from pysgmcmc_amd import kernels
+    B, L = int(X.shape[0]), len(hs) - 1
+    forward, h = [], X
+    for l in range(L + 1):
+        W = params[2 * l]
+        fits = l < L and fused_layers and kernels.bnn_dense_tanh_fits(h, W, hs[l]) and pays(B, int(W.shape[1]))
+        if l == L:
+            forward.append("by rowdot" if single_out else "addmm")
+        elif l == L - 1 and single_out:
+            # with the output unit's dot product in the launch, the loss head must add the partials: the fused head only
+            top_fits = fits and fused_head and (B // 32) * (int(W.shape[1]) // 64) >= 16 and B <= 1024
+            forward.append("dense_tanh+dot" if top_fits else "mm+bias_tanh_rowdot")
+        else:
+            forward.append("dense_tanh" if fits else "mm+bias_tanh")
+        h = hs[l]
+    return forward
+
+
+def _plan_ones_row(params, grad_views, X, ext, n_hidden, fused_layers, fold_prior):
+    """[W_0 ; b_0] must be one contiguous matrix in the gradient arena (and in theta's when the prior rides in the product)."""
+    adjacent = lambda a, b: (a.is_contiguous() and b.is_contiguous()
+                             and b.data_ptr() == a.data_ptr() + a.numel() * a.element_size())
+    return bool(fused_layers and ext is not None and n_hidden >= 2 and X.shape[0] == ext.shape[0]
+                and X.stride(0) == ext.stride(0) and ext.shape[1] > int(X.shape[1]) and adjacent(grad_views[0], grad_views[1])
+                and (fold_prior or adjacent(params[0], params[1])))
+
+
+def _plan_backward(params, hs, ds, fused_layers, pays, single_out, fused_head, ones_row):
+    from pysgmcmc_amd import kernels
+    B, L = int(hs[0].shape[0]), len(hs) - 1
+    backward = {}
+    for l in range(L, 0, -1):
+        if l == L and fused_head:
+            backward[l] = "in head launch"
+        elif l == L and single_out:
+            backward[l] = "last_layer_backward"
+        elif (fused_layers and kernels.bnn_dense_tanh_backward_fits(ds[l], params[2 * l], hs[l - 1], ds[l - 1])
+              and pays(B, int(params[2 * l].shape[0]))):
+            backward[l] = "dense_tanh_backward"
+        else:
+            backward[l] = "mm+tanh_backward" if (l == 1 and ones_row) else "mm+tanh_backward_colsum"
+    return backward
+
+
+def _plan_gw_batch(params, grad_views, hs, ds, single_out, fold_prior):
+    """Weight gradients of consecutive hidden layers of one shape as ONE strided batched product (2 x [2048 x 2048 x 256]: 34.9 us
+    against 41.5 for two products in a row): layers lo .. hi whose inputs h_{l-1}, deltas, gradient slices (and, with the prior
+    in the product, weights) lie at one constant stride each. ``(lo, hi, s_h, s_d, s_g, s_w)`` or None."""
+    L = len(hs) - 1
+    hi = L - 1 if single_out else L
+    for lo in range(1, hi):
+        run = range(lo, hi + 1)
+        if not all(params[2 * l].shape == params[2 * lo].shape and hs[l - 1].shape == hs[lo - 1].shape for l in run):
+            continue
+        strides = [_stride_of([hs[l - 1] for l in run]), _stride_of([ds[l] for l in run]), _stride_of([grad_views[2 * l] for l in run]),
+                   0 if fold_prior else _stride_of([params[2 * l] for l in run])]
+        if None not in strides and hs[0].is_cuda:
+            return (lo, hi) + tuple(strides)
+    return None
+
+
+def _plan_gw_planes(params, gw_batch, setting, fold_prior, dtype, B, cus):
+    """The batched product on the bf16 matrix pipe (BNNCost.gw_on_bf16_planes): True where the shapes fit, "auto" from 4 tiles of
+    128 x 128 per compute unit."""
+    if gw_batch is None or not setting or not fold_prior or dtype != torch.float32 or B % 16:
+        return False
+    lo, hi = gw_batch[0], gw_batch[1]
+    fan_in, fan_out = (int(v) for v in params[2 * lo].shape)
+    tiles = (hi - lo + 1) * ((fan_in + 127) // 128) * ((fan_out + 127) // 128)
+    return setting is True or tiles >= 4 * max(cus, 1)
 
 
 class BNNCost(object):
@@ -320,6 +413,9 @@ class BNNCost(object):
         return ext[:, :value.shape[1]]
 
     def _buffers(self, params, B):
+        """Workspace of one (batch, dtype, device, layer widths): what that key fixes -- activations ``"h"``, deltas ``"d"``,
+        ``"ones"``, ``"tsq_parts"``, ``"cost"``, ``"mse"`` -- and ``"scratch"``, the pool :meth:`_scratch` hands plan scratch out
+        of. Only this method and :meth:`_scratch` write into it. Another key replaces the workspace AND drops every plan made on it."""
         n_layers = (len(params) - 1) // 2
         widths = [params[2 * l].shape[1] for l in range(n_layers)]
         key = (B, params[0].dtype, params[0].device, tuple(widths))
@@ -341,13 +437,21 @@ class BNNCost(object):
                 return out
             ws = {"h": rows_of(widths), "d": rows_of(widths),
                   "ones": torch.ones(B, dtype=dt, device=dev),
-                  # per-column-tile partial dot products of the last hidden layer with the output unit's weights (bnn_dense_tanh)
-                  "dot_parts": None,
                   "tsq_parts": torch.zeros(16, dtype=torch.float64, device=dev),
-                  "cost": torch.zeros(1, dtype=dt, device=dev), "mse": torch.zeros(1, dtype=dt, device=dev)}
+                  "cost": torch.zeros(1, dtype=dt, device=dev), "mse": torch.zeros(1, dtype=dt, device=dev), "scratch": {}}
             self._ws = {key: ws}
             self._plans = collections.OrderedDict()
         return ws
+
+    @staticmethod
+    def _scratch(ws, name, numel, dtype, device, zero):
+        """The workspace's ``numel`` elements of ``dtype`` called ``name``: the pooled tensor if there is one, else a new one
+        (zeroed if ``zero``) that joins the pool. Grow-only and held strongly: no entry is replaced or removed, so what a plan was
+        given stays at its address as long as the workspace lives (an evicted plan's captured graph may still replay)."""
+        pool, key = ws["scratch"], (name, int(numel), dtype)
+        if key not in pool:
+            pool[key] = (torch.zeros if zero else torch.empty)(int(numel), dtype=dtype, device=device)
+        return pool[key]
 
     @torch.no_grad()
     def cost_and_grad(self, params, grad_views, theta_sumsq=None, theta_sumsq_partials=None):
@@ -392,86 +496,36 @@ class BNNCost(object):
         if plan is not None:
             self._plans.move_to_end(key)
             return plan
-        B, n_layers = int(X.shape[0]), (len(params) - 1) // 2
-        L = n_layers - 1
+        B, L = int(X.shape[0]), (len(params) - 1) // 2 - 1
         hs, ds = ws["h"], ws["d"]
-        single_out = params[2 * L].shape[1] == 1 and n_layers >= 2
+        single_out = params[2 * L].shape[1] == 1 and L >= 1
         fused_head = single_out and have_partials
         cus = torch.cuda.get_device_properties(X.device).multi_processor_count if X.is_cuda else 0
         # the fused launch pays while its workgroups run as ONE round (see __init__); "all": wherever the kernel takes the shape
         pays = lambda rows, cols: self.fused_layers == "all" or (rows // 32) * (cols // 64) <= cus
-        forward, h = [], X
-        for l in range(n_layers):
-            W = params[2 * l]
-            fits = l < L and self.fused_layers and kernels.bnn_dense_tanh_fits(h, W, hs[l]) and pays(B, int(W.shape[1]))
-            if l == L:
-                forward.append("by rowdot" if single_out else "addmm")
-            elif l == L - 1 and single_out:
-                # with the output unit's dot product in the launch, the loss head must add the partials: the fused head only
-                top_fits = fits and fused_head and (B // 32) * (int(W.shape[1]) // 64) >= 16 and B <= 1024
-                forward.append("dense_tanh+dot" if top_fits else "mm+bias_tanh_rowdot")
-                if top_fits and ws["dot_parts"] is None:
-                    ws["dot_parts"] = torch.zeros(kernels.bnn_dense_tanh_dot_parts(B, int(W.shape[1]), X.device), B, dtype=X.dtype, device=X.device)
-            else:
-                forward.append("dense_tanh" if fits else "mm+bias_tanh")
-            h = hs[l]
         ext = self._x_ext.get(X.data_ptr())
-        D_in = int(X.shape[1])
-        adjacent = lambda a, b: (a.is_contiguous() and b.is_contiguous()
-                                 and b.data_ptr() == a.data_ptr() + a.numel() * a.element_size())
-        # [W_0 ; b_0] must be one contiguous matrix in the gradient arena (and in theta's when the prior rides in the product)
-        ones_row = (self.fused_layers and ext is not None and L >= 2 and X.shape[0] == ext.shape[0]
-                    and X.stride(0) == ext.stride(0) and ext.shape[1] > D_in and adjacent(grad_views[0], grad_views[1])
-                    and (self.fold_prior or adjacent(params[0], params[1])))
-        backward = {}
-        for l in range(L, 0, -1):
-            if l == L and fused_head:
-                backward[l] = "in head launch"
-            elif l == L and single_out:
-                backward[l] = "last_layer_backward"
-            elif (self.fused_layers and kernels.bnn_dense_tanh_backward_fits(ds[l], params[2 * l], hs[l - 1], ds[l - 1])
-                  and pays(B, int(params[2 * l].shape[0]))):
-                backward[l] = "dense_tanh_backward"
-            else:
-                backward[l] = "mm+tanh_backward" if (l == 1 and ones_row) else "mm+tanh_backward_colsum"
-        if "dense_tanh_backward" in backward.values() and "colsum_parts" not in ws:
+        forward = _plan_forward(params, X, hs, self.fused_layers, pays, single_out, fused_head)
+        ones_row = _plan_ones_row(params, grad_views, X, ext, L, self.fused_layers, self.fold_prior)
+        backward = _plan_backward(params, hs, ds, self.fused_layers, pays, single_out, fused_head, ones_row)
+        gw_batch = _plan_gw_batch(params, grad_views, hs, ds, single_out, self.fold_prior)
+        gw_planes = _plan_gw_planes(params, gw_batch, self.gw_on_bf16_planes, self.fold_prior, X.dtype, B, cus)
+        # scratch of the launches just chosen, from the workspace's pool (sizes follow from the workspace key and gw_batch)
+        scratch = lambda name, numel, dtype, zero: self._scratch(ws, name, numel, dtype, X.device, zero)
+        dot_parts = colsum_parts = planes_h = planes_d = None
+        if "dense_tanh+dot" in forward:
+            # per-column-tile partial dot products of the last hidden layer with the output unit's weights (bnn_dense_tanh)
+            n_parts = kernels.bnn_dense_tanh_dot_parts(B, int(params[2 * (L - 1)].shape[1]), X.device)
+            dot_parts = scratch("dot_parts", n_parts * B, X.dtype, True).view(n_parts, B)
+        if "dense_tanh_backward" in backward.values():
             widest = max(int(p.shape[0]) for p in params[0:-1:2])
-            ws["colsum_parts"] = [torch.zeros((B // 32) * widest, dtype=X.dtype, device=X.device) for _ in range(2)]
-        # weight gradients of consecutive hidden layers of one shape as ONE strided batched product (2 x [2048 x 2048 x 256]: 34.9 us
-        # against 41.5 for two products in a row): layers lo .. hi whose inputs h_{l-1}, deltas, gradient slices (and, with the prior
-        # in the product, weights) lie at one constant stride each
-        gw_batch = None
-
-        def stride_of(ts):
-            """Elements between consecutive tensors of ``ts`` if they are contiguous, equally spaced views of ONE allocation, else None."""
-            base = ts[0].untyped_storage().data_ptr()
-            if not all(t.is_contiguous() and t.untyped_storage().data_ptr() == base for t in ts):
-                return None                                       # (one strided view must be able to span them: one allocation)
-            gaps = {ts[k + 1].data_ptr() - ts[k].data_ptr() for k in range(len(ts) - 1)}
-            gap = gaps.pop() if len(gaps) == 1 else 0
-            return gap // ts[0].element_size() if gap > 0 and gap % ts[0].element_size() == 0 else None
-        hi = L - 1 if single_out else L
-        for lo in range(1, hi):
-            run = range(lo, hi + 1)
-            if not all(params[2 * l].shape == params[2 * lo].shape and hs[l - 1].shape == hs[lo - 1].shape for l in run):
-                continue
-            strides = [stride_of([hs[l - 1] for l in run]), stride_of([ds[l] for l in run]), stride_of([grad_views[2 * l] for l in run]),
-                       0 if self.fold_prior else stride_of([params[2 * l] for l in run])]
-            if None not in strides and hs[0].is_cuda:
-                gw_batch = (lo, hi) + tuple(strides)
-                break
-        gw_planes = False
-        if gw_batch is not None and self.gw_on_bf16_planes and self.fold_prior and X.dtype == torch.float32 and B % 16 == 0:
-            lo, hi = gw_batch[0], gw_batch[1]
-            fan_in, fan_out = (int(v) for v in params[2 * lo].shape)
-            tiles = (hi - lo + 1) * ((fan_in + 127) // 128) * ((fan_out + 127) // 128)
-            if self.gw_on_bf16_planes is True or tiles >= 4 * max(cus, 1):
-                gw_planes = True
-                n = hi - lo + 1
-                ws["planes_h"] = torch.empty(n * kernels.bnn_planes_bytes(B, fan_in), dtype=torch.uint8, device=X.device)
-                ws["planes_d"] = torch.empty(n * kernels.bnn_planes_bytes(B, fan_out), dtype=torch.uint8, device=X.device)
-        plan = _CostPlan(forward, "head+last_layer_backward" if fused_head else "head", backward, bool(ones_row),
-                         ext[:, :D_in + 1] if ones_row else None, single_out, gw_batch, gw_planes)
+            colsum_parts = [scratch("colsum_parts%d" % k, (B // 32) * widest, X.dtype, True) for k in range(2)]
+        if gw_planes:
+            n, (fan_in, fan_out) = gw_batch[1] - gw_batch[0] + 1, params[2 * gw_batch[0]].shape
+            planes_h = scratch("planes_h", n * kernels.bnn_planes_bytes(B, fan_in), torch.uint8, False)
+            planes_d = scratch("planes_d", n * kernels.bnn_planes_bytes(B, fan_out), torch.uint8, False)
+        plan = _CostPlan(forward, "head+last_layer_backward" if fused_head else "head", backward, ones_row,
+                         ext[:, :int(X.shape[1]) + 1] if ones_row else None, single_out, gw_batch, gw_planes,
+                         dot_parts=dot_parts, colsum_parts=colsum_parts, planes_h=planes_h, planes_d=planes_d)
         self._plans[key] = plan
         while len(self._plans) > self.MAX_CACHED_PLANS:
             self._plans.popitem(last=False)                      # least recently used; its feed buffer goes with its last user
@@ -486,34 +540,39 @@ class BNNCost(object):
         X, Y = self.x_placeholder.value, self.y_placeholder.value
         ws = self._buffers(params, X.shape[0])
         plan = self._plan(params, grad_views, X, ws, theta_sumsq_partials is not None)
-        if plan.fresh and not X.is_cuda:
-            plan.fresh = False                                    # (host tensors: the kernels below refuse them, loudly)
         if plan.fresh:
             plan.fresh = False
-            import torch.cuda.tunable as tunable
-            n_total = sum(int(p.numel()) for p in params)
-            walk = lambda: self._walk_plan(plan, params, grad_views, theta_sumsq, theta_sumsq_partials, X, Y, ws)
-            by_caller = tunable.is_enabled() and tunable.tuning_is_enabled()
-            device_bound = n_total >= AUTO_GEMM_TUNING_MIN_PARAMS and not torch.cuda.is_current_stream_capturing()
-            if by_caller or (self.auto_gemm_tuning and device_bound):
-                self.gemm_tuning_applied = "caller" if by_caller else "auto"
-                if device_bound:
-                    # the library's own picks first: candidates should not be timed on a device that has just woken up (clocks
-                    # still ramping, cold caches)
-                    if by_caller:
-                        tunable.tuning_enable(False)
-                    try:
-                        for _ in range(self.AUTO_GEMM_TUNING_WARM_EVALUATIONS):
-                            walk()
-                    finally:
-                        if by_caller:
-                            tunable.tuning_enable(True)
-                if by_caller:
-                    return walk()                                 # tuned under the caller's own TunableOp settings
-                with _GemmTuningScope():
-                    return walk()
-            self.gemm_tuning_applied = "off"
+            if X.is_cuda:                                         # (host tensors: the kernels of the walk refuse them, loudly)
+                return self._first_evaluation(plan, params, grad_views, theta_sumsq, theta_sumsq_partials, X, Y, ws)
         return self._walk_plan(plan, params, grad_views, theta_sumsq, theta_sumsq_partials, X, Y, ws)
+
+    def _first_evaluation(self, plan, params, grad_views, theta_sumsq, theta_sumsq_partials, X, Y, ws):
+        """The first walk of a plan: where ``auto_gemm_tuning`` (or the caller's own TunableOp settings) picks the library GEMM
+        solutions of a device-bound plan by measurement. Sets ``gemm_tuning_applied``; returns the cost like every walk."""
+        import torch.cuda.tunable as tunable
+        n_total = sum(int(p.numel()) for p in params)
+        walk = lambda: self._walk_plan(plan, params, grad_views, theta_sumsq, theta_sumsq_partials, X, Y, ws)
+        by_caller = tunable.is_enabled() and tunable.tuning_is_enabled()
+        device_bound = n_total >= AUTO_GEMM_TUNING_MIN_PARAMS and not torch.cuda.is_current_stream_capturing()
+        if not (by_caller or (self.auto_gemm_tuning and device_bound)):
+            self.gemm_tuning_applied = "off"
+            return walk()
+        self.gemm_tuning_applied = "caller" if by_caller else "auto"
+        if device_bound:
+            # the library's own picks first: candidates should not be timed on a device that has just woken up (clocks
+            # still ramping, cold caches)
+            if by_caller:
+                tunable.tuning_enable(False)
+            try:
+                for _ in range(self.AUTO_GEMM_TUNING_WARM_EVALUATIONS):
+                    walk()
+            finally:
+                if by_caller:
+                    tunable.tuning_enable(True)
+        if by_caller:
+            return walk()                                         # tuned under the caller's own TunableOp settings
+        with _GemmTuningScope():
+            return walk()
 
     def _walk_plan(self, plan, params, grad_views, theta_sumsq, theta_sumsq_partials, X, Y, ws):
         from pysgmcmc_amd import kernels
@@ -527,9 +586,9 @@ class BNNCost(object):
             if op == "dense_tanh":
                 kernels.bnn_dense_tanh(h, W, b.view(-1), hs[l])
             elif op == "dense_tanh+dot":
-                kernels.bnn_dense_tanh(h, W, b.view(-1), hs[l], w_next=params[2 * L].view(-1), dot_parts=ws["dot_parts"],
+                kernels.bnn_dense_tanh(h, W, b.view(-1), hs[l], w_next=params[2 * L].view(-1), dot_parts=plan.dot_parts,
                                        stats_workspace=theta_sumsq_partials, tsq_parts=ws["tsq_parts"])
-                mean = ws["dot_parts"]
+                mean = plan.dot_parts
             elif op == "mm+bias_tanh":
                 # plain product, the bias rides in the activation launch (the library's plain GEMM is 1.4-2.1 us faster than its
                 # bias-epilogue one at batch 256, round 3)
@@ -599,7 +658,7 @@ class BNNCost(object):
                 parts = None
                 if not (l == 1 and plan.ones_row):
                     n_tiles, width = B // 32, int(W.shape[0])
-                    parts = ws["colsum_parts"][parts_turn][:n_tiles * width].view(n_tiles, width)
+                    parts = plan.colsum_parts[parts_turn][:n_tiles * width].view(n_tiles, width)
                     parts_turn ^= 1
                 kernels.bnn_dense_tanh_backward(ds[l], W, hs[l - 1], ds[l - 1], colsum_parts=parts, finish=pending)
                 pending = None if parts is None else (parts, grad_views[2 * (l - 1) + 1], params[2 * (l - 1) + 1].view(-1), beta)
@@ -610,9 +669,9 @@ class BNNCost(object):
                 lo, hi, s_h, s_d, s_g, s_w = plan.gw_batch
                 if l == lo and plan.gw_planes:                    # ... on the bf16 matrix pipe: both operands as 3 exact planes first
                     run = range(lo, hi + 1)
-                    kernels.bnn_split_planes([hs[k - 1] for k in run], ws["planes_h"])
-                    kernels.bnn_split_planes([ds[k] for k in run], ws["planes_d"])
-                    kernels.bnn_gw_planes(ws["planes_h"], ws["planes_d"], [grad_views[2 * k] for k in run], B)
+                    kernels.bnn_split_planes([hs[k - 1] for k in run], plan.planes_h)
+                    kernels.bnn_split_planes([ds[k] for k in run], plan.planes_d)
+                    kernels.bnn_gw_planes(plan.planes_h, plan.planes_d, [grad_views[2 * k] for k in run], B)
                 elif l == lo:                                     # the last delta of the group exists now: ONE strided batched product
                     n = hi - lo + 1
                     stack = lambda t, st: torch.as_strided(t, (n,) + tuple(t.shape), (st,) + tuple(t.stride()))

@@ -288,3 +288,55 @@ def test_auto_gemm_tuning_has_an_environment_opt_out(monkeypatch):
     from pysgmcmc_amd.models.bayesian_neural_network import BNNCost
     monkeypatch.setenv("PYSGMCMC_AMD_AUTO_GEMM_TUNING", "0")
     assert BNNCost(None, None, batch_size=4, n_examples=10).auto_gemm_tuning is False
+
+
+def test_plan_scratch_pool_is_grow_only():
+    """``BNNCost._scratch``: one pooled tensor per (name, numel, dtype) of a workspace; another size is another tensor and leaves
+    the first where it was; names asked for zeroed come back zeroed."""
+    params = init_mlp_params(64, hidden=(128, 128), seed=1, dtype=torch.float32)
+    c = BNNCost(Placeholder().feed(torch.zeros(64, 64)), Placeholder().feed(torch.zeros(64, 1)), batch_size=64, n_examples=100)
+    ws = c._buffers(params, 64)
+    dev = torch.device("cpu")
+    a = c._scratch(ws, "planes_h", 96, torch.uint8, dev, False)
+    ptr = a.data_ptr()
+    assert a.shape == (96,) and a.dtype == torch.uint8
+    assert c._scratch(ws, "planes_h", 96, torch.uint8, dev, False) is a
+    b = c._scratch(ws, "planes_h", 192, torch.uint8, dev, False)
+    assert b is not a and b.numel() == 192 and b.data_ptr() != ptr
+    assert c._scratch(ws, "planes_h", 96, torch.uint8, dev, False) is a and a.data_ptr() == ptr
+    assert c._scratch(ws, "planes_h", 96, torch.float32, dev, False) is not a              # the dtype is part of the key
+    z = c._scratch(ws, "colsum_parts0", 640, torch.float32, dev, True)
+    assert z.dtype == torch.float32 and z.numel() == 640 and not z.any()
+    assert c._scratch(ws, "colsum_parts0", 640, torch.float32, dev, True) is z
+    assert c._buffers(params, 64) is ws                                                   # same key: same workspace, same pool
+    assert c._scratch(ws, "planes_h", 192, torch.uint8, dev, False) is b
+
+
+def test_building_plans_leaves_the_workspace_as_its_key_fixed_it():
+    """Plans take scratch from the workspace's pool and put nothing else into the workspace: its keys are the same before and
+    after plans with and without statistics partials, with ``fused_layers`` on and off. Each plan is what the commit before the
+    pool returned for the same call (recorded from it on host tensors)."""
+    params = init_mlp_params(64, hidden=(128, 128), seed=1, dtype=torch.float32)
+    xp, yp = Placeholder().feed(torch.zeros(64, 64)), Placeholder().feed(torch.zeros(64, 1))
+    c = BNNCost(xp, yp, batch_size=64, n_examples=100)
+    grads = [torch.zeros_like(p) for p in params]
+    ws = c._buffers(params, 64)
+    keys = set(ws)
+    assert keys == {"h", "d", "ones", "tsq_parts", "cost", "mse", "scratch"}
+    want = {False: {"forward": ["mm+bias_tanh", "mm+bias_tanh_rowdot", "by rowdot"], "head": "head",
+                    "backward": {2: "last_layer_backward", 1: "mm+tanh_backward_colsum"},
+                    "first_layer_bias_gradient": "column sums"},
+            True: {"forward": ["mm+bias_tanh", "mm+bias_tanh_rowdot", "by rowdot"], "head": "head+last_layer_backward",
+                   "backward": {2: "in head launch", 1: "mm+tanh_backward_colsum"},
+                   "first_layer_bias_gradient": "column sums"}}
+    plans = []
+    for fused in (True, False):
+        for partials in (False, True):
+            c.fused_layers = fused
+            plan = c._plan(params, grads, xp.value, c._buffers(params, 64), partials)
+            assert plan.as_dict() == want[partials], (fused, partials)
+            assert c._buffers(params, 64) is ws and set(ws) == keys
+            # library products only on host tensors: no launch of these plans needs scratch
+            assert plan.dot_parts is None and plan.colsum_parts is None and plan.planes_h is None and plan.planes_d is None
+            plans.append(plan)
+    assert len({id(p) for p in plans}) == 4 and list(c._plans.values()) == plans

@@ -435,3 +435,77 @@ def test_cost_path_with_the_weight_gradients_on_bf16_planes(gpu, hidden, setting
     # fold_prior = False needs beta * W in the product's epilogue: that plan keeps the library
     cost.fold_prior = False
     assert cost.plan_summary(params, grads, st.workspace)["batched_weight_gradient_arithmetic"].startswith("library fp32")
+
+
+def test_a_captured_plan_keeps_its_plane_buffers_when_other_plans_are_built(gpu):
+    """A plan carries the scratch its launches write, handed out by the workspace's grow-only pool: a hipGraph captured from
+    plan A's walk holds the addresses of A's bf16 plane buffers, so plans built afterwards on the same cost (``plan_summary``
+    without statistics partials, ``fused_layers`` / ``gw_on_bf16_planes`` toggled and back) must leave those two tensors where
+    they are and share them. Replayed after all that, with fresh tensors of the planes' size around, the graph gives the same
+    gradient bits and writes into none of them."""
+    from pysgmcmc_amd import kernels
+    from pysgmcmc_amd.samplers.base_classes import graph_capture
+    cost, params = _cost(gpu, True, 32, (128, 128, 128), n_in=64, own_feed_buffer=True)
+    cost.gw_on_bf16_planes = True
+    assert cost.fold_prior is True
+    n = sum(p.numel() for p in params)
+    flat = torch.cat([p.reshape(-1) for p in params])
+    offs = np.cumsum([0] + [p.numel() for p in params])
+    params = [flat[offs[k]:offs[k + 1]].view(p.shape) for k, p in enumerate(params)]
+    gflat = torch.full((n,), float("nan"), device=gpu)
+    grads = [gflat[offs[k]:offs[k + 1]].view(p.shape) for k, p in enumerate(params)]
+    st = kernels.StepStats(n, gpu)
+    kernels.sghmc_step(flat.clone(), torch.zeros(n, device=gpu), torch.zeros(n, device=gpu), None, None, None,
+                       torch.ones(n, device=gpu), None, 0.0, 1.0, 0.0, False, xi=torch.zeros(n, device=gpu), stats=st,
+                       opts=dict(theta_sq_only=True))
+    X = cost.x_placeholder.value
+    evaluate = lambda: cost.cost_and_grad(params, grads, theta_sumsq_partials=st.workspace)
+    plan_a = lambda: cost._plan(params, grads, X, cost._buffers(params, 32), True)
+    # 1: plan A, evaluated once
+    A = plan_a()
+    assert A.gw_planes and A.gw_batch[:2] == (1, 2)
+    planes = (A.planes_h, A.planes_d)
+    ptrs = tuple(t.data_ptr() for t in planes)
+    assert all(t.dtype == torch.uint8 and t.numel() == 2 * kernels.bnn_planes_bytes(32, 128) for t in planes) and ptrs[0] != ptrs[1]
+    evaluate()
+    eager = gflat.clone()
+    assert torch.isfinite(eager).all()
+    # 2: one more evaluation of plan A, captured (warm-up on a side stream first, as the samplers capture their cost pipeline)
+    cur, side = torch.cuda.current_stream(gpu), torch.cuda.Stream(device=gpu)
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        evaluate()
+    cur.wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with graph_capture(graph, capture_error_mode="thread_local"):
+        evaluate()
+    gflat.fill_(float("nan"))
+    graph.replay()
+    replayed = gflat.clone()
+    assert torch.equal(replayed, eager)
+    # 3: further plans on the same cost
+    assert cost.plan_summary(params, grads)["batched_weight_gradient_arithmetic"].startswith("3 exact bf16 planes")
+    cost.fused_layers = False
+    assert cost.plan_summary(params, grads, st.workspace)["forward"][0] == "mm+bias_tanh"
+    cost.fused_layers = True
+    cost.gw_on_bf16_planes = "auto"
+    assert cost.plan_summary(params, grads, st.workspace)["batched_weight_gradient_arithmetic"] == "library fp32 product"
+    cost.gw_on_bf16_planes = True
+    # 4: plan A is still the plan of its key, with the tensors it had; every later plan on the planes shares them
+    assert plan_a() is A and A.planes_h is planes[0] and A.planes_d is planes[1]
+    assert tuple(t.data_ptr() for t in planes) == ptrs
+    later = [p for p in cost._plans.values() if p is not A]
+    assert len(later) == 3 and sum(p.gw_planes for p in later) == 2
+    for p in later:
+        if p.gw_planes:
+            assert p.planes_h is planes[0] and p.planes_d is planes[1]
+        else:
+            assert p.planes_h is None and p.planes_d is None
+    # 5: whatever the allocator hands out now is not the planes' memory: the replay leaves it alone and computes the same bits
+    canaries = [torch.full((planes[0].numel(),), 0x5A, dtype=torch.uint8, device=gpu) for _ in range(4)]
+    gflat.fill_(float("nan"))
+    graph.replay()
+    torch.cuda.synchronize(gpu)
+    assert torch.equal(gflat, replayed)
+    assert all(bool((t == 0x5A).all()) for t in canaries)
+    del graph
