@@ -3,7 +3,7 @@
 Drop-in for ``pysgmcmc.samplers`` / ``pysgmcmc.sampling`` (SGLD, SGHMC,
 relativistic SGHMC): same class names, constructor keywords, ``next(sampler)``
 iterator protocol. The per-parameter update runs as one fused HIP kernel per
-step (``csrc/sgmcmc_kernels.hip``) reached through the C ABI in
+step (``csrc/sgmcmc_sghmc.hip`` and its siblings) reached through the C ABI in
 ``include/sgmcmc_hip.h``; there is no CPU fallback.
 
     from pysgmcmc_amd.samplers import SGHMCSampler, SGLDSampler, RelativisticSGHMCSampler

@@ -7,7 +7,7 @@ CPU fallback: if the shared library is missing or a call fails, a
 import ctypes
 import os
 
-__all__ = ["SgmcmcLibraryError", "lib", "lib_path", "check", "build"]
+__all__ = ["SgmcmcLibraryError", "lib", "lib_path", "check", "build", "build_dependencies"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
@@ -23,15 +23,19 @@ def lib_path():
     return _LIB_PATH
 
 
+def build_dependencies():
+    """Every file the library is built from, as found on disk: the translation units, their headers and the Makefile in
+    ``csrc/``, and the public headers in ``include/``. ``build()`` rebuilds when one of them is newer than the library."""
+    import glob
+    include = os.path.join(os.path.dirname(_HERE), "include")
+    return sorted(glob.glob(os.path.join(_CSRC, "*.hip")) + glob.glob(os.path.join(_CSRC, "*.hpp"))
+                  + [os.path.join(_CSRC, "Makefile")] + glob.glob(os.path.join(include, "*.h")))
+
+
 def build(force=False):
     """Compile ``csrc/libsgmcmc_hip.so`` for gfx950 with hipcc (no GPU needed)."""
     import subprocess
-    deps = [os.path.join(_CSRC, f) for f in ("sgmcmc_kernels.hip", "sgmcmc_sghmc.hip", "sgmcmc_sgld.hip", "sgmcmc_rsghmc.hip", "sgmcmc_toy.hip", "sgmcmc_bnn_gemm.hip", "sgmcmc_stream.hpp", "sgmcmc_bnn_fused.hip", "sgmcmc_svgd.hip", "sgmcmc_device.hpp",
-                                             "sgmcmc_host.hpp", "sgmcmc_ess.hip", "sgmcmc_scalars.hpp")]
-    deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip.h"))
-    deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip_diag.h"))
-    deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip_fused.h"))
-    deps.append(os.path.join(os.path.dirname(_HERE), "include", "sgmcmc_hip_fused_trace.h"))
+    deps = build_dependencies()
     stale = (not os.path.exists(_LIB_PATH)
              or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(d) for d in deps))
     if force or stale:

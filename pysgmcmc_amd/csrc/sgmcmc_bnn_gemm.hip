@@ -51,6 +51,7 @@
 #pragma clang fp contract(off)
 
 #include "sgmcmc_host.hpp"
+#include "sgmcmc_stats_ws.hpp"
 
 using namespace sgmcmc_host;
 
@@ -62,7 +63,6 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 constexpr int BM = 32, BK = 64;
 // BN (template parameter of the kernel): 64 = the tile the pipeline was built for -- 8 waves = 2 MFMA tiles x 4 K quarters; 32 = the
 // HALF tile of a launch's last, partly filled round of workgroups -- 8 waves = 1 MFMA tile x 8 K eighths (see the entry points)
-constexpr int TSQ_SLICES = 16;                              // as sgmcmc_kernels.hip: slices of the sum(theta^2) partials
 
 // s_waitcnt immediate on gfx9: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14; expcnt / lgkmcnt = no wait
 constexpr int vmcnt_imm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
@@ -318,11 +318,8 @@ __global__ void __launch_bounds__(512, 2) bnn_dense_tanh_kernel(const FwdArgs g)
     const unsigned n_slices = gridDim.x < (unsigned)TSQ_SLICES ? gridDim.x : (unsigned)TSQ_SLICES;
     const bool slicer = !BWD && g.stats_ws != nullptr && blockIdx.x < n_slices;
     if (slicer) {
-        const unsigned nparts = (unsigned)reinterpret_cast<const unsigned long long *>(g.stats_ws)[0];
-        const double *__restrict__ p = g.stats_ws + 4;
-        const unsigned len = (nparts + n_slices - 1) / n_slices;
-        const unsigned lo = blockIdx.x * len, hi = (lo + len < nparts) ? lo + len : nparts;
-        for (unsigned i = lo + tid; i < hi; i += 512) tsq += p[4 * (size_t)i];      // statistic 0 of record i
+        const StatsSlice sl = stats_ws_slice(stats_ws_records(g.stats_ws), n_slices, blockIdx.x);
+        for (unsigned i = sl.lo + tid; i < sl.hi; i += 512) tsq += stats_ws_stat(g.stats_ws, i);
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) tsq += __shfl_down(tsq, off, 64);
     }

@@ -187,8 +187,7 @@ __device__ __forceinline__ T adapt_stats(T grad, T &tau, T &g, T &vh, T &r_out)
 }
 
 // One parameter's SGHMC update given its (possibly decayed) gradient gr, preconditioner mi and normal draw z
-// (sghmc.py:211-243 with fed / freshly adapted minv). Shared by the streaming operator below and by the epilogue of the
-// weight-gradient GEMM (sgmcmc_gemm.hip), so both give the same bits.
+// (sghmc.py:211-243 with fed / freshly adapted minv): the streaming operator below calls it once per element of a quad.
 template <typename T>
 __device__ __forceinline__ void sghmc_elem_update(T &th, T &v, T gr, T mi, T z, T e2, T c1, T c3, T e4, T mdecay)
 {

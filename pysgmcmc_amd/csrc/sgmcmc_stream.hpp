@@ -1,8 +1,8 @@
 // sgmcmc_stream.hpp -- the ONE streaming kernel shape every per-element operator of libsgmcmc_hip.so shares
 // (stream_quads_vec / stream_quads_scalar), its fused statistics reduction, the fused Welford moments, and the host-side
 // launch logic. Included by the per-sampler translation units (sgmcmc_sghmc.hip, sgmcmc_sgld.hip, sgmcmc_rsghmc.hip)
-// and by sgmcmc_kernels.hip; everything lives in an anonymous namespace (one copy per translation unit, compiled side
-// by side by `make -j`).
+// and by sgmcmc_kernels.hip (the Philox fill and the moments); everything lives in an anonymous namespace (one copy per
+// translation unit, compiled side by side by `make -j`).
 //
 // HBM-bound elementwise pass, no contraction => no MFMA, no LDS staging of the streamed arrays. Work unit = one
 // "quad" of 4 consecutive elements per lane: 16 B per lane per array (global_load/store_dwordx4, 1 KiB per wave

@@ -3,7 +3,7 @@ hot subset only: vectorize :17-104, unvectorize :107-153, safe_divide :211-269,
 safe_sqrt :272-323, uninitialized_params :579-605).
 
 In the kernels ``safe_divide`` / ``safe_sqrt`` are device functions
-(``csrc/sgmcmc_kernels.hip``: ``sdiv`` / ``ssqrt``); the torch versions here serve
+(``csrc/sgmcmc_device.hpp``: ``sdiv`` / ``ssqrt``); the torch versions here serve
 host-side code such as the BNN priors. ``vectorize`` needs no shadow variable:
 the flat arena already *is* the vectorized parameter.
 """

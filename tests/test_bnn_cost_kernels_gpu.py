@@ -1,4 +1,4 @@
-"""The BNN cost path's small kernels (csrc/sgmcmc_kernels.hip, and the sum(theta^2) slicing side job of
+"""The BNN cost path's small kernels (csrc/sgmcmc_bnn_cost.hip, and the sum(theta^2) slicing side job of
 csrc/sgmcmc_bnn_gemm.hip), each called directly and compared element by element with a float64 numpy reference computed
 from the same (already rounded) inputs:
 
@@ -612,6 +612,35 @@ def test_fused_head_at_the_log_var_extremes(gpu, dt):
     for s in (-40.0, 20.0):
         _fused_case(gpu, dt, rng, 257, 50, 1, BETA, False, True, True, s=s, compare_separate=True)
         _fused_case(gpu, dt, rng, 1000, 17, 33, BETA, False, True, True, s=s)
+
+
+ONE_HEAD_SHAPES = [(r, c) for r in (1, 63, 65, 257, 1025) for c in (1, 17)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", DTS)
+def test_the_plain_and_the_fused_head_are_one_head(gpu, dt):
+    """bnn_head (sum(theta^2) given directly) and bnn_head_last_layer_backward (one mean part, the same total as small
+    integers in tsq_parts) on identical inputs: cost, d cost/d log_var, the last-bias gradient and mse are the same bits,
+    and the fused delta_prev[r][c] is (delta[r] * w[c]) * (1 - h[r][c]^2) formed in T from the plain head's delta. Rows: one
+    lane, either side of a wave, past one four-row trip, past one 1024-lane block stride; columns: one, one past a block."""
+    rng = np.random.RandomState(18)
+    one = NPT[dt](1)
+    for i, (rows, cols) in enumerate(ONE_HEAD_SHAPES):
+        fold, add_bias = bool(i & 1), bool(i & 2)
+        k = _consts(rows)
+        lb, s, bt = float(NPT[dt](-0.3)), float(NPT[dt](0.7)), float(NPT[dt](BETA))
+        mean, y = _head_inputs(rng, rows, dt, lb, add_bias)
+        h, w, bias = _col_case_inputs(rng, rows, cols, dt)
+        slices = rng.randint(1, 40, min(16, rows)).astype(np.float64)
+        db, sc_plain = _run_head(gpu, dt, mean, y, s, lb, k, fold, add_bias, True, tsq_scalar=float(slices.sum()))
+        sc_fused, dpb, _, _ = _run_fused(gpu, dt, mean[None, :], y, s, slices, lb, k, fold, add_bias, True, h, w, bias, bt)
+        assert _same_bits(sc_plain, sc_fused), (rows, cols, sc_plain.tolist(), sc_fused.tolist())
+        delta = db[:rows].cpu().numpy()
+        hT, wT = np.asarray(h, NPT[dt]).reshape(rows, cols), np.asarray(w, NPT[dt])
+        want = (delta[:, None] * wT[None, :]) * (one - hT * hT)          # one rounding per operation, in T
+        got = dpb[:rows * cols].cpu().numpy().reshape(rows, cols)
+        assert want.dtype == got.dtype and np.array_equal(got.view(np.uint8), want.view(np.uint8)), (rows, cols)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -116,6 +116,23 @@ def test_library_contains_gfx950_code_object():
     assert "gfx950" in out
 
 
+def test_build_dependencies_cover_every_file_the_makefile_names():
+    """``_lib.build()`` rebuilds when a dependency is newer than the library: every translation unit and header the Makefile
+    compiles from (SRCS, HDRS) must be one, or editing it would leave a stale library in place."""
+    from pysgmcmc_amd import _lib
+    text = open(os.path.join(ROOT, "pysgmcmc_amd", "csrc", "Makefile")).read().replace("\\\n", " ")
+    named = []
+    for var in ("SRCS", "HDRS"):
+        named += re.search(r"^%s\s*:=(.*)$" % var, text, re.M).group(1).split()
+    assert len(named) >= 15, named
+    deps = _lib.build_dependencies()
+    assert all(os.path.isfile(d) for d in deps), deps
+    have = {os.path.basename(d) for d in deps}
+    missing = [n for n in named if os.path.basename(n) not in have]
+    assert not missing, missing
+    assert {"sgmcmc_bnn_gw.hip", "sgmcmc_bnn_cost.hip", "Makefile"} <= have
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "pysgmcmc_amd")
     offenders = []

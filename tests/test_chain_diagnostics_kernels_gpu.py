@@ -1,4 +1,5 @@
-"""The chain diagnostics kernels (csrc/sgmcmc_kernels.hip, the ``[boundary]`` group of include/sgmcmc_hip.h), each called
+"""The chain diagnostics kernels (csrc/sgmcmc_kernels.hip, which holds the ``[boundary]`` group of include/sgmcmc_hip.h apart
+from the sampler steps; K4's operator is ``MomentsOp`` in csrc/sgmcmc_device.hpp), each called
 directly through ``pysgmcmc_amd.kernels`` in f32 and f64 and compared with a float64 reference:
 
 - K4 ``moments_update``: bit-equal to the C oracle's Welford at every size, alignment and launch geometry, and within a
