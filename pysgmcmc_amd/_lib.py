@@ -95,25 +95,19 @@ def _declare(lib):
     lib.sgmcmc_event_elapsed_ms.restype = _ci
     lib.sgmcmc_event_synchronize.argtypes = [_vp]
     lib.sgmcmc_event_synchronize.restype = _ci
+    # The per-step update entries (sgmcmc_hip.h [boundary]): state pointers, n, the kind's by-value scalars (eps first),
+    # grad_decay, [adapt,] xi, seed, step, step_dev, stats_ws, opts, launch, stream; their scalars twins: the same scalars,
+    # scalars_dev, stream. kind: (state pointers, by-value scalars, adapt flag)
+    per_step = {"sghmc": (8, 3, True), "sgld": (7, 3, True), "rsghmc": (3, 5, False)}
     for sfx, real in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
-        f = getattr(lib, "sgmcmc_sghmc_step_" + sfx)
-        f.argtypes = [_vp] * 8 + [_sz, real, real, real, real, _ci, _vp, _u64, _u64, _vp, _vp, _op, _lp, _vp]
-        f.restype = _ci
-        f = getattr(lib, "sgmcmc_sgld_step_" + sfx)
-        f.argtypes = [_vp] * 7 + [_sz, real, real, real, real, _ci, _vp, _u64, _u64, _vp, _vp, _op, _lp, _vp]
-        f.restype = _ci
-        f = getattr(lib, "sgmcmc_rsghmc_step_" + sfx)
-        f.argtypes = [_vp] * 3 + [_sz, real, real, real, real, real, real, _vp, _u64, _u64, _vp, _vp, _op, _lp, _vp]
-        f.restype = _ci
-        f = getattr(lib, "sgmcmc_sghmc_scalars_" + sfx)
-        f.argtypes = [real, real, real, _vp, _vp]
-        f.restype = _ci
-        f = getattr(lib, "sgmcmc_sgld_scalars_" + sfx)
-        f.argtypes = [real, real, real, _vp, _vp]
-        f.restype = _ci
-        f = getattr(lib, "sgmcmc_rsghmc_scalars_" + sfx)
-        f.argtypes = [real, real, real, real, real, _vp, _vp]
-        f.restype = _ci
+        for kind, (n_rows, n_scalars, adapt) in per_step.items():
+            f = getattr(lib, "sgmcmc_%s_step_%s" % (kind, sfx))
+            f.argtypes = ([_vp] * n_rows + [_sz] + [real] * (n_scalars + 1) + ([_ci] if adapt else [])
+                          + [_vp, _u64, _u64, _vp, _vp, _op, _lp, _vp])
+            f.restype = _ci
+            f = getattr(lib, "sgmcmc_%s_scalars_%s" % (kind, sfx))
+            f.argtypes = [real] * n_scalars + [_vp, _vp]
+            f.restype = _ci
         f = getattr(lib, "sgmcmc_toy_chains_" + sfx)
         f.argtypes = [_ci, _ci, ctypes.POINTER(ctypes.c_double), _ci] + [_vp] * 6 + [_sz, _ci, ctypes.POINTER(ctypes.c_double),
                       _vp, _u64, _u64, ctypes.c_int64, _u64, _vp, _vp]

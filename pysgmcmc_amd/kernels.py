@@ -13,7 +13,7 @@ import torch
 from pysgmcmc_amd._lib import SgmcmcLibraryError, check, lib
 
 __all__ = [
-    "sghmc_step", "sgld_step", "rsghmc_step", "philox_normal", "philox_bits",
+    "sghmc_step", "sgld_step", "rsghmc_step", "update_step", "philox_normal", "philox_bits",
     "moments_update", "rhat_pack", "rhat_finish", "summary",
     "LaunchConfig", "KernelEvents", "StepOpts", "step_stats_records", "step_scalars", "toy_chains", "set_launch_config", "get_launch_config", "summary_workspace", "counter_add", "StepStats", "bnn_head", "bnn_dense_tanh_backward", "bnn_dense_tanh_backward_fits", "colsum_finish", "tanh_backward", "tanh_backward_colsum", "bnn_last_layer_backward", "bnn_fused_sghmc_steps", "step_stats_finish",
     "bnn_fused_sgld_steps", "bnn_fused_rsghmc_steps", "bnn_fused_steps", "step_scalars_table", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
@@ -276,39 +276,38 @@ def step_scalars(kind, out, *scalars):
     return out
 
 
+def update_step(kind, rows, scalars, adapt=None, xi=None, seed=0, step=0, step_dev=None, stats=None, grad_decay=0.0, launch=None,
+                opts=None):
+    """``sgmcmc_<kind>_step_*``, one update launch in place: the state ``rows`` in the entry's order (theta first), its by-value
+    ``scalars`` (eps first), the ``adapt`` flag of a burn-in kind (None: the kind has none), then what all kinds take."""
+    theta = rows[0]
+    f = getattr(lib(), "sgmcmc_%s_step_%s" % (kind, _sfx(theta)))
+    with _on(theta):
+        rc = f(*[_ptr(t, theta) for t in rows], theta.numel(), *[float(v) for v in scalars], float(grad_decay),
+               *(() if adapt is None else (int(bool(adapt)),)), _ptr(xi, theta), int(seed), int(step), _ctr(step_dev),
+               *_stats(stats), _opts(opts, theta), _launch(launch), _stream(theta))
+    check(rc, "sgmcmc_%s_step" % kind)
+
+
 def sghmc_step(theta, V, grad, tau, g, v_hat, minv, r, eps, scale_grad, mdecay, adapt, xi=None, seed=0, step=0, step_dev=None,
                stats=None, grad_decay=0.0, launch=None, opts=None):
     """K1, one fused SGHMC step in place (pysgmcmc/samplers/sghmc.py:165-251)."""
-    f = getattr(lib(), "sgmcmc_sghmc_step_" + _sfx(theta))
-    with _on(theta):
-        rc = f(_ptr(theta), _ptr(V, theta), _ptr(grad, theta), _ptr(tau, theta), _ptr(g, theta),
-               _ptr(v_hat, theta), _ptr(minv, theta), _ptr(r, theta), theta.numel(),
-               float(eps), float(scale_grad), float(mdecay), float(grad_decay), int(bool(adapt)), _ptr(xi, theta),
-               int(seed), int(step), _ctr(step_dev), *_stats(stats), _opts(opts, theta), _launch(launch), _stream(theta))
-    check(rc, "sgmcmc_sghmc_step")
+    update_step("sghmc", (theta, V, grad, tau, g, v_hat, minv, r), (eps, scale_grad, mdecay), adapt, xi, seed, step, step_dev,
+                stats, grad_decay, launch, opts)
 
 
 def sgld_step(theta, grad, tau, g, v_hat, minv, r, eps, A, scale_grad, adapt, xi=None, seed=0, step=0, step_dev=None,
               stats=None, grad_decay=0.0, launch=None, opts=None):
     """K2, one fused SGLD step in place (pysgmcmc/samplers/sgld.py:149-211)."""
-    f = getattr(lib(), "sgmcmc_sgld_step_" + _sfx(theta))
-    with _on(theta):
-        rc = f(_ptr(theta), _ptr(grad, theta), _ptr(tau, theta), _ptr(g, theta), _ptr(v_hat, theta),
-               _ptr(minv, theta), _ptr(r, theta), theta.numel(), float(eps), float(A), float(scale_grad),
-               float(grad_decay), int(bool(adapt)), _ptr(xi, theta), int(seed), int(step), _ctr(step_dev), *_stats(stats),
-               _opts(opts, theta), _launch(launch), _stream(theta))
-    check(rc, "sgmcmc_sgld_step")
+    update_step("sgld", (theta, grad, tau, g, v_hat, minv, r), (eps, A, scale_grad), adapt, xi, seed, step, step_dev,
+                stats, grad_decay, launch, opts)
 
 
 def rsghmc_step(theta, p, grad_cost, eps, mass, c, D, b_hat, xi=None, seed=0, step=0, step_dev=None,
                 stats=None, grad_decay=0.0, launch=None, opts=None):
     """K3, one fused relativistic SGHMC step (pysgmcmc/samplers/relativistic_sghmc.py:120-140)."""
-    f = getattr(lib(), "sgmcmc_rsghmc_step_" + _sfx(theta))
-    with _on(theta):
-        rc = f(_ptr(theta), _ptr(p, theta), _ptr(grad_cost, theta), theta.numel(), float(eps), float(mass),
-               float(c), float(D), float(b_hat), float(grad_decay), _ptr(xi, theta), int(seed), int(step), _ctr(step_dev), *_stats(stats),
-               _opts(opts, theta), _launch(launch), _stream(theta))
-    check(rc, "sgmcmc_rsghmc_step")
+    update_step("rsghmc", (theta, p, grad_cost), (eps, mass, c, D, b_hat), None, xi, seed, step, step_dev,
+                stats, grad_decay, launch, opts)
 
 
 def toy_chains(sampler, target, target_params, theta, mom, tau, g, v_hat, minv, scalars, seeds, first_step, n_steps,

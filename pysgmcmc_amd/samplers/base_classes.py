@@ -105,6 +105,8 @@ class MCMCSampler(object):
     # "sghmc" / "sgld" / "rsghmc": the kernel can read its stepsize-derived scalars from a device block
     # (kernels.step_scalars); None: by value only
     _SCALARS_KIND = None
+    # the state rows of that kernel's entry point, in its order (theta first)
+    _STEP_ROWS = ()
     MAX_STEPSIZE_GRAPHS = 4               # use_hip_graph='full' on a by-value stepsize kernel: graphs kept (least recently used one evicted)
     # every parameter starts at a multiple of this many elements in the arena rows (1 = dense)
     _PARAM_ALIGN = 1
@@ -348,7 +350,17 @@ class MCMCSampler(object):
     def _kernel_step(self, eps, xi, sl=None, opts=None):
         """Launch the update of the elements ``sl`` (a slice of the arena rows; None = all) with the step extras
         ``opts`` (a dict of ``kernels.StepOpts`` keywords or None)."""
-        raise NotImplementedError
+        if not self._STEP_ROWS:
+            raise NotImplementedError
+        more_rows, flags = self._step_extra_args(sl)
+        step = getattr(kernels, self._SCALARS_KIND + "_step")       # kernels.sghmc_step / sgld_step / rsghmc_step
+        step(*self._sliced_rows(self._STEP_ROWS, sl), *more_rows, *self._step_scalars(eps), *flags, xi=xi, stats=self._step_stats(),
+             grad_decay=self._grad_decay, launch=self._launch(), opts=opts, **self._noise_args())
+        self._stats_written()
+
+    def _step_extra_args(self, sl):
+        """(rows behind ``_STEP_ROWS``, flags behind the scalars) of the kernel's entry point: none without a burn-in."""
+        return (), ()
 
     def _bytes_per_element(self):
         """Bytes one update launch touches per parameter (mirrors the library's auto-geometry rule)."""
@@ -772,6 +784,10 @@ class BurnInMCMCSampler(MCMCSampler):
         mean = s[0] / n
         var = max(s[1] / n - mean * mean, 0.0)
         return {"mean": mean, "std": var ** 0.5, "min": s[2], "max": s[3]}
+
+    def _step_extra_args(self, sl):
+        r = self._r_row()
+        return (r if (r is None or sl is None) else r[sl],), (self._adapting,)
 
     def _r_row(self):
         if not self.materialize_r:

@@ -142,9 +142,4 @@ class RelativisticSGHMCSampler(FusedBNNStepsMixin, MCMCSampler):
     def _step_scalars(self, eps):
         return (eps, self.mass, self.speed_of_light, self.D, self.Bhat)
 
-    def _kernel_step(self, eps, xi, sl=None, opts=None):
-        rows = self._sliced_rows(("theta", "p", "grad"), sl)
-        kernels.rsghmc_step(
-            *rows, eps, self.mass, self.speed_of_light, self.D, self.Bhat,
-            xi=xi, stats=self._step_stats(), grad_decay=self._grad_decay, launch=self._launch(), opts=opts, **self._noise_args())
-        self._stats_written()
+    _STEP_ROWS = ("theta", "p", "grad")

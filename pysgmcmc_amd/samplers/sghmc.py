@@ -6,7 +6,6 @@ g, v_hat, noise scale, momentum, theta) is kernel K1,
 """
 import torch
 
-from pysgmcmc_amd import kernels
 from pysgmcmc_amd.samplers._fused_bnn import FusedBNNStepsMixin
 from pysgmcmc_amd.samplers.base_classes import BurnInMCMCSampler
 from pysgmcmc_amd.stepsize_schedules import ConstantStepsizeSchedule
@@ -44,11 +43,4 @@ class SGHMCSampler(FusedBNNStepsMixin, BurnInMCMCSampler):
     def _step_scalars(self, eps):
         return (eps, self.scale_grad, self.mdecay)
 
-    def _kernel_step(self, eps, xi, sl=None, opts=None):
-        rows = self._sliced_rows(("theta", "V", "grad", "tau", "g", "v_hat", "minv"), sl)
-        r = self._r_row()
-        kernels.sghmc_step(
-            *rows, r if (r is None or sl is None) else r[sl],
-            eps, self.scale_grad, self.mdecay, self._adapting,
-            xi=xi, stats=self._step_stats(), grad_decay=self._grad_decay, launch=self._launch(), opts=opts, **self._noise_args())
-        self._stats_written()
+    _STEP_ROWS = ("theta", "V", "grad", "tau", "g", "v_hat", "minv")

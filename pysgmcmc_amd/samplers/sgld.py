@@ -5,7 +5,6 @@ The per-step op chain ``sgld.py:149-211`` is kernel K2,
 """
 import torch
 
-from pysgmcmc_amd import kernels
 from pysgmcmc_amd.samplers._fused_bnn import FusedBNNStepsMixin
 from pysgmcmc_amd.samplers.base_classes import BurnInMCMCSampler
 from pysgmcmc_amd.stepsize_schedules import ConstantStepsizeSchedule
@@ -60,11 +59,4 @@ class SGLDSampler(FusedBNNStepsMixin, BurnInMCMCSampler):
     def _step_scalars(self, eps):
         return (eps, self.A, self.scale_grad)
 
-    def _kernel_step(self, eps, xi, sl=None, opts=None):
-        rows = self._sliced_rows(("theta", "grad", "tau", "g", "v_hat", "minv"), sl)
-        r = self._r_row()
-        kernels.sgld_step(
-            *rows, r if (r is None or sl is None) else r[sl],
-            eps, self.A, self.scale_grad, self._adapting,
-            xi=xi, stats=self._step_stats(), grad_decay=self._grad_decay, launch=self._launch(), opts=opts, **self._noise_args())
-        self._stats_written()
+    _STEP_ROWS = ("theta", "grad", "tau", "g", "v_hat", "minv")

@@ -230,3 +230,75 @@ def test_dense_layer_column_plan_without_a_device():
     assert parts(256, 4864) == 64 + 24                           # configs[4]: 512 full tiles + the last 12 column tiles as 24 half tiles
     assert parts(256, 4096 + 64 * 20) == (4096 + 64 * 20) // 64  # a last round more than half full stays on full tiles
     assert parts(20, 2048) == 0 and parts(256, 100) == 0         # shapes the launch refuses
+
+
+# state pointers / by-value scalars (eps first) of sgmcmc_<kind>_step_*; the burn-in kinds take an adapt flag behind grad_decay
+_STEP_ENTRIES = {"sghmc": (8, 3), "sgld": (7, 3), "rsghmc": (3, 5)}
+
+
+def _step_call(lib, kind, sfx, rows, n=4, adapt=0, stats_ws=None, opts=None, launch=None):
+    n_rows, n_scalars = _STEP_ENTRIES[kind]
+    rows = [4096 * (k + 1) for k in range(n_rows)] if rows is None else rows        # never dereferenced: the call fails first
+    flag = [] if kind == "rsghmc" else [adapt]
+    f = getattr(lib, "sgmcmc_%s_step_%s" % (kind, sfx))
+    return f(*rows, n, *[0.01] * (n_scalars + 1), *flag, None, 1, 0, None, stats_ws, opts, launch, None)
+
+
+def test_step_entries_refuse_bad_arguments_before_any_launch():
+    """The per-step entries validate on the host, in a fixed order, before the first HIP call: return code and
+    ``sgmcmc_last_error()`` text of every refusal (the texts an integrator's logs carry), on a machine without a device."""
+    from pysgmcmc_amd import _lib
+    lib = _lib.lib()
+    required = {"sghmc": b"sghmc_step: theta, V, grad and minv must be non-NULL",
+                "sgld": b"sgld_step: theta, grad and minv must be non-NULL",
+                "rsghmc": b"rsghmc_step: theta, p and grad_cost must be non-NULL"}
+    needs = {"sghmc": b"sghmc_step: adapt=1 needs tau, g and v_hat", "sgld": b"sgld_step: adapt=1 needs tau, g and v_hat"}
+    gather = dict(gather_x=4096, gather_y=8192, gather_x_out=12288, gather_y_out=16384, gather_batch=32, gather_x_out_ld=16)
+    bad_opts = [
+        (dict(first_element=2), None, b"%s_step: opts.first_element must be a multiple of 4 (slices start on a quad)"),
+        (dict(stats_select=7), None, b"%s_step: opts.stats_select must be 0 (all) or SGMCMC_STATS_THETA_SQ"),
+        (dict(stats_record_total=1), None, b"%s_step: opts.stats_record_* without a stats workspace"),
+        (dict(moments_mean=4096), None, b"%s_step: opts.moments_mean and opts.moments_m2 go together"),
+        (dict(moments_mean=4096, moments_m2=8192, moments_count=0), None, b"%s_step: opts.moments_count must be >= 1"),
+        (dict(gather_dim=0, **gather), None,
+         b"%s_step: opts.gather_* needs X, y, both outputs, batch > 0, dim > 0 and x_out_ld >= dim"),
+        (None, _lib.LaunchStruct(100, 0, 0, -1), b"launch.block_threads must be 64, 128, 192, 256, 0 (default) or -1 (auto)"),
+    ]
+    for sfx in ("f32", "f64"):
+        for kind, (n_rows, n_scalars) in _STEP_ENTRIES.items():
+            assert _step_call(lib, kind, sfx, [None] * n_rows) == -1
+            assert lib.sgmcmc_last_error() == required[kind]
+            # n == 0 returns before the NULL checks and leaves the previous error text in place
+            assert _step_call(lib, kind, sfx, [None] * n_rows, n=0, adapt=1) == 0
+            assert lib.sgmcmc_last_error() == required[kind]
+            if kind in needs:
+                rows = [4096 * (k + 1) for k in range(n_rows)]
+                for k in range(n_rows - 5, n_rows - 2):                             # tau, g, v_hat
+                    assert _step_call(lib, kind, sfx, rows[:k] + [None] + rows[k + 1:], adapt=1) == -1
+                    assert lib.sgmcmc_last_error() == needs[kind]
+            for fields, launch, text in bad_opts:
+                opts = None if fields is None else ctypes.byref(_lib.StepOptsStruct(**fields))
+                assert _step_call(lib, kind, sfx, None, opts=opts, launch=None if launch is None else ctypes.byref(launch)) == -1
+                assert lib.sgmcmc_last_error() == (text % kind.encode() if b"%s" in text else text)
+            scalars = getattr(lib, "sgmcmc_%s_scalars_%s" % (kind, sfx))
+            assert scalars(*[0.01] * n_scalars, None, None) == -1
+            assert lib.sgmcmc_last_error() == b"%s_scalars: scalars_dev is NULL" % kind.encode()
+
+
+def test_step_entries_are_declared_with_the_header_s_argument_types():
+    """``_lib._declare`` builds the twelve per-step declarations from one table: the lists it must produce, written out."""
+    from pysgmcmc_amd import _lib
+    lib = _lib.lib()
+    vp, sz, ci, u64, op, lp = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint64, _lib._op, _lib._lp
+    for sfx, real in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        want = {
+            "sgmcmc_sghmc_step_": [vp, vp, vp, vp, vp, vp, vp, vp, sz, real, real, real, real, ci, vp, u64, u64, vp, vp, op, lp, vp],
+            "sgmcmc_sgld_step_": [vp, vp, vp, vp, vp, vp, vp, sz, real, real, real, real, ci, vp, u64, u64, vp, vp, op, lp, vp],
+            "sgmcmc_rsghmc_step_": [vp, vp, vp, sz, real, real, real, real, real, real, vp, u64, u64, vp, vp, op, lp, vp],
+            "sgmcmc_sghmc_scalars_": [real, real, real, vp, vp],
+            "sgmcmc_sgld_scalars_": [real, real, real, vp, vp],
+            "sgmcmc_rsghmc_scalars_": [real, real, real, real, real, vp, vp],
+        }
+        for name, argtypes in want.items():
+            f = getattr(lib, name + sfx)
+            assert list(f.argtypes) == argtypes and f.restype is ci, name + sfx

@@ -220,6 +220,20 @@ def test_register_noise_equals_injected_stream(gpu, oracle, npdt, thdt):
         kernels.set_launch_config()           # back to the library defaults (a Python-side default, not library state)
     for r in results[1:]:
         assert torch.equal(results[0], r)     # geometry never changes the samples
+    # the relativistic step at m = c = 1 and at an m^2 c^2 that is no power of two (its other in-register instantiation):
+    # one 256-lane block of quads plus a 3-element tail
+    n = 1027
+    grad = _dev(rng.normal(size=n).astype(npdt), gpu)
+    for mass, c in [(1.0, 1.0), (1.3, 0.7)]:
+        cst = oracle.CState(th0[:n], npdt)
+        cst.p[:] = rng.normal(size=n).astype(npdt)
+        a, b = GpuState(cst, gpu), GpuState(cst, gpu)
+        for t in range(3):
+            xi = torch.empty(n, dtype=thdt, device=gpu)
+            kernels.philox_normal(xi, 2024, t)
+            kernels.rsghmc_step(a.theta, a.p, grad, 0.001, mass, c, 1.0, 0.0, xi=None, seed=2024, step=t)
+            kernels.rsghmc_step(b.theta, b.p, grad, 0.001, mass, c, 1.0, 0.0, xi=xi)
+            assert torch.equal(a.theta, b.theta) and torch.equal(a.p, b.p)
 
 
 def test_concurrent_host_threads_with_their_own_launch_geometry(gpu, oracle):
