@@ -11,7 +11,11 @@
 // small BNN); it is latency-bound by design (one dependent chain per lane).
 //
 // Gradients: cost = -log_likelihood (compute_ess.py:170-174, tests/samplers/sampler_testing.py:14-18), derivatives
-// written out in the op order of the CPU restatement under oracle/ (gmm_cost_grad, banana), which tests/ compares it with.
+// written out in the op order of the CPU restatement under oracle/ (gmm_cost_grad, banana). tests/toy_reference.py restates
+// all three in numpy, one rounding per op, and tests/test_toy_chains_kernel_gpu.py reads this kernel's gradient at 4099
+// points per target through a one-step relativistic probe and compares it with that restatement and with long double, in
+// f32 and f64; the same file pins every sampler's step bit for bit (the scalars A.s[] below included), short free-running
+// chains, the kept layout, 64-bit step indices and every refusal.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -180,12 +184,15 @@ int toy_chains(int sampler, int target, const double *tp, int k, T *theta, T *mo
 {
     if (n_chains == 0 || n_steps == 0) return 0;
     if (sampler < 0 || sampler > 2) return fail(SGMCMC_EINVAL, "toy_chains: sampler must be 0 (SGHMC), 1 (SGLD) or 2 (relativistic SGHMC)");
-    if (!theta || !seeds || !sc || (sampler != 1 && !mom) || (sampler != 2 && (!tau || !g || !vh || !minv)))
-        return fail(SGMCMC_EINVAL, "toy_chains: NULL state array");
+    if (!theta || !seeds || !sc) return fail(SGMCMC_EINVAL, "toy_chains: NULL theta, seeds or scalars");
+    if (sampler != 1 && !mom) return fail(SGMCMC_EINVAL, "toy_chains: NULL mom (SGHMC and relativistic SGHMC own a momentum)");
+    if (sampler != 2 && (!tau || !g || !vh || !minv))
+        return fail(SGMCMC_EINVAL, "toy_chains: NULL tau, g, v_hat or minv (SGHMC and SGLD own the adaptation statistics)");
     if (keep_every == 0) return fail(SGMCMC_EINVAL, "toy_chains: keep_every must be >= 1");
-    const int want_dim = target == 0 ? 1 : 2;
-    if (target < 0 || target > 2 || dim != want_dim) return fail(SGMCMC_EINVAL, "toy_chains: target 0 (1-D mixture) has dim 1, 1 (banana) and 2 (2-D mixture) dim 2");
-    if (target != 1 && (!tp || k < 1 || k > TOY_MAX_K)) return fail(SGMCMC_EINVAL, "toy_chains: mixtures take 1..16 components");
+    if (target < 0 || target > 2) return fail(SGMCMC_EINVAL, "toy_chains: target must be 0 (1-D mixture), 1 (banana) or 2 (2-D mixture)");
+    if (dim != (target == 0 ? 1 : 2)) return fail(SGMCMC_EINVAL, "toy_chains: target 0 (1-D mixture) has dim 1, 1 (banana) and 2 (2-D mixture) dim 2");
+    if (target != 1 && !tp) return fail(SGMCMC_EINVAL, "toy_chains: NULL target_params for a mixture");
+    if (target != 1 && (k < 1 || k > TOY_MAX_K)) return fail(SGMCMC_EINVAL, "toy_chains: mixtures take 1..16 components");
     ToyArgs<T> A;
     A.target = target; A.k = k; A.dim = dim;
     for (int i = 0; i < TOY_MAX_K; ++i) { A.a[i] = A.b[i] = A.mu[i] = T(0); A.var[i] = T(1); }

@@ -319,9 +319,13 @@ def toy_chains(sampler, target, target_params, theta, mom, tau, g, v_hat, minv, 
     f = getattr(lib(), "sgmcmc_toy_chains_" + _sfx(theta))
     n_chains, dim = int(theta.shape[0]), int(theta.shape[1])
     tp = [float(v) for v in target_params]
-    k = {0: len(tp) // 3, 1: 0, 2: len(tp) // 2}[int(target)]
+    k = {0: len(tp) // 3, 2: len(tp) // 2}.get(int(target), 0)        # an unknown target is the library's to refuse
     if seeds.dtype != torch.int64 or seeds.numel() != n_chains:
         raise TypeError("seeds must be an int64 device tensor with one entry per chain")
+    if int(keep_every) < 1:
+        raise ValueError("keep_every must be >= 1")
+    if int(n_steps) < 0 or int(first_step) < 0:
+        raise ValueError("first_step and n_steps are unsigned step counts")
     n_kept = (int(n_steps) + int(keep_every) - 1) // int(keep_every)
     if kept is not None and (kept.numel() != n_kept * n_chains * dim or kept.dtype != theta.dtype):
         raise ValueError("kept must hold ceil(n_steps / keep_every) x n_chains x dim elements of theta's dtype")

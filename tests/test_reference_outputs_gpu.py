@@ -7,8 +7,11 @@ and Philox stream of kernel K3), both with the default initial-momentum draw and
 (one host draw per parameter tensor, relativistic_sghmc.py:108-113).
 
 Chain of evidence: reference outputs == oracle at the full protocol (tests/test_reference_outputs.py, CPU);
-oracle == HIP kernels bit for bit per step (tests/test_hip_parity.py); toy path == public sampler API
-(tests/test_builtin_target_chains_gpu.py); here: HIP == reference in the statistic itself, at full strength.
+oracle == HIP kernels bit for bit per step (tests/test_hip_parity.py); toy path == public sampler API in f64
+(tests/test_builtin_target_chains_gpu.py) and, in the f32 these runs use, == the oracle's step fed the toy kernel's own
+gradient, bit for bit, with that gradient pinned to a rounded numpy restatement and to long double
+(tests/test_toy_chains_kernel_gpu.py, reference validated in tests/test_toy_reference.py); here: HIP == reference in
+the statistic itself, at full strength.
 """
 import numpy as np
 import pytest
