@@ -48,8 +48,10 @@ ABI_VERSION = 6               # SGMCMC_ABI_VERSION of include/sgmcmc_hip.h
 DIAG_ABI_VERSION = 1          # SGMCMC_DIAG_ABI_VERSION of include/sgmcmc_hip_diag.h (the diagnostics add-on)
 FUSED_ABI_VERSION = 1         # SGMCMC_FUSED_ABI_VERSION of include/sgmcmc_hip_fused.h (the whole-step add-on)
 FUSED_TRACE_ABI_VERSION = 1   # SGMCMC_FUSED_TRACE_ABI_VERSION of include/sgmcmc_hip_fused_trace.h (the thinned-trace add-on)
+PREDICT_ABI_VERSION = 1       # SGMCMC_PREDICT_ABI_VERSION of include/sgmcmc_hip_predict.h (the posterior-predictive add-on)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
+PREDICT_MAX_CHAINS = 64
 
 _u64 = ctypes.c_uint64
 _sz = ctypes.c_size_t
@@ -220,6 +222,15 @@ def _declare(lib):
         f.argtypes = ([_ci, ctypes.POINTER(_vp), _ci] + net + [ctypes.POINTER(real), _ci, _vp] + [_u64] * 4
                       + [_vp, _vp, _vp, _sz] + [_u64] * 4 + [_vp])
         f.restype = _ci
+    # include/sgmcmc_hip_predict.h: host array of chain matrices, m, n, ld, layer sizes, n_layers, X, n_rows, means, noise_var,
+    # ens_mean, ens_var, stream
+    lib.sgmcmc_predict_abi_version.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_bnn_predict_" + sfx)
+        f.argtypes = [ctypes.POINTER(_vp), _ci, _sz, _sz, ctypes.POINTER(_ci), _ci, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
+        f.restype = _ci
+    lib.sgmcmc_bnn_predict_row_tile.argtypes = [ctypes.POINTER(_ci), _ci, _sz]
+    lib.sgmcmc_bnn_predict_row_tile.restype = _ci
 
 
 def lib():
@@ -244,6 +255,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: whole-step add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_fused_trace_abi_version() != FUSED_TRACE_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: thinned-trace add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_predict_abi_version() != PREDICT_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: posterior-predictive add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

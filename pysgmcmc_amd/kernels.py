@@ -17,7 +17,7 @@ __all__ = [
     "moments_update", "rhat_pack", "rhat_finish", "summary",
     "LaunchConfig", "KernelEvents", "StepOpts", "step_stats_records", "step_scalars", "toy_chains", "set_launch_config", "get_launch_config", "summary_workspace", "counter_add", "StepStats", "bnn_head", "bnn_dense_tanh_backward", "bnn_dense_tanh_backward_fits", "colsum_finish", "tanh_backward", "tanh_backward_colsum", "bnn_last_layer_backward", "bnn_fused_sghmc_steps", "step_stats_finish",
     "bnn_fused_sgld_steps", "bnn_fused_rsghmc_steps", "bnn_fused_steps", "step_scalars_table", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
-    "ess_variogram",
+    "ess_variogram", "bnn_predict", "bnn_predict_row_tile",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -461,6 +461,94 @@ def ess_variogram(chains, ess, raw=None, stop_lag=None, ld=None, staging="auto",
         rc = f(table, len(mats), n, P, ld, _ptr(ess), _ptr(raw), _ptr(stop_lag), stage, _launch(launch), _stream(first))
     check(rc, "sgmcmc_ess_variogram")
     return ess
+
+
+def _bnn_n_params(sizes):
+    return sum(sizes[l] * sizes[l + 1] + sizes[l + 1] for l in range(len(sizes) - 1)) + 1
+
+
+def bnn_predict_row_tile(layer_sizes, dtype=torch.float32):
+    """Test rows per tile of ``bnn_predict``'s forward launch for this net and dtype (``sgmcmc_bnn_predict_row_tile``:
+    host arithmetic, nothing launched). Performance only; the results do not depend on it."""
+    import ctypes
+    sizes = [int(v) for v in layer_sizes]
+    esize = {torch.float32: 4, torch.float64: 8}[dtype]
+    tile = lib().sgmcmc_bnn_predict_row_tile((ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, esize)
+    if tile < 1:
+        check(tile, "sgmcmc_bnn_predict_row_tile")
+    return tile
+
+
+def bnn_predict(chains, layer_sizes, X, means, noise_var=None, ens_mean=None, ens_var=None):
+    """K11 (``include/sgmcmc_hip_predict.h``): the outputs of ``S`` sampled networks of a small tanh-MLP BNN at the rows
+    of ``X``, read from device traces, and their ensemble moments, in one call without host synchronisation.
+
+    ``chains``: one ``(m, n, P)`` device tensor, one ``(n, P)`` tensor, or a sequence of ``m <= 64`` ``(n, P)`` tensors
+    that live in buffers of their own; sample ``s = c * n + i`` is row ``i`` of chain ``c``, a flat parameter vector in
+    the whole-step kernel's order (``P >= n_params``; what lies behind ``n_params`` is not read). Rows must be dense and
+    all chains share one row pitch, as for ``ess_variogram``; a 3-D tensor whose chains lie back to back goes down as ONE
+    matrix of ``m * n`` rows, so it may hold more than 64 chains. ``X``: ``(N, layer_sizes[0])``, contiguous, the chains'
+    dtype. ``means``: ``(S, N)`` of that dtype, required (also the reduction's only scratch). ``noise_var``: ``(S,)`` of
+    that dtype or None. ``ens_mean``, ``ens_var``: float64 ``(N,)``, both or neither. Returns ``means``."""
+    import ctypes
+    if torch.is_tensor(chains):
+        if chains.dim() == 2:
+            mats = [chains]
+        elif chains.dim() == 3:
+            m3, n3, P3 = (int(v) for v in chains.shape)
+            if m3 >= 1 and n3 >= 1 and (m3 == 1 or chains.stride(0) == n3 * chains.stride(1)):
+                # the chains lie back to back at one row pitch: one matrix of m * n rows, no pointer table
+                mats = [chains.as_strided((m3 * n3, P3), (chains.stride(1), chains.stride(2)), chains.storage_offset())]
+            else:
+                mats = list(chains.unbind(0))
+        else:
+            raise ValueError("bnn_predict: chains must be (n, P), (m, n, P) or a sequence of (n, P) tensors")
+    else:
+        mats = list(chains)
+    if not mats:
+        raise ValueError("bnn_predict: no chains")
+    first = mats[0]
+    for x in mats:
+        if not x.is_cuda:
+            raise SgmcmcLibraryError("pysgmcmc_amd: trace lives on %s; the posterior predictive of device traces runs "
+                                     "only as a HIP kernel on an AMD GPU (no CPU fallback)." % x.device)
+        if x.dim() != 2 or x.shape != first.shape:
+            raise ValueError("bnn_predict: every chain must be an (n, P) matrix of the same shape")
+        if x.dtype != first.dtype or x.device != first.device:
+            raise TypeError("bnn_predict: the chains must share a dtype and a device")
+    f = getattr(lib(), "sgmcmc_bnn_predict_" + _sfx(first))
+    sizes = [int(v) for v in layer_sizes]
+    n, P = int(first.shape[0]), int(first.shape[1])
+    if len(sizes) < 2 or P < _bnn_n_params(sizes):
+        raise ValueError("bnn_predict: the traces are %d wide, layer sizes %s need %d parameters" % (
+            P, sizes, _bnn_n_params(sizes) if len(sizes) >= 2 else -1))
+    ld = int(first.stride(0)) if n > 1 else P
+    for x in mats:
+        if (P > 1 and x.stride(1) != 1) or (n > 1 and x.stride(0) != ld):
+            raise ValueError("bnn_predict: rows must be dense and %d elements apart in every chain" % ld)
+    if not torch.is_tensor(X) or X.dtype != first.dtype or X.device != first.device:
+        raise TypeError("bnn_predict: X must be a %s tensor on %s" % (first.dtype, first.device))
+    if X.dim() != 2 or int(X.shape[1]) != sizes[0] or not X.is_contiguous():
+        raise ValueError("bnn_predict: X must be a contiguous (N, %d) matrix, got %s" % (sizes[0], tuple(X.shape)))
+    S, N = len(mats) * n, int(X.shape[0])
+    for out, dt, numel, name in ((means, first.dtype, S * N, "means"), (noise_var, first.dtype, S, "noise_var"),
+                                 (ens_mean, torch.float64, N, "ens_mean"), (ens_var, torch.float64, N, "ens_var")):
+        if out is None:
+            if name == "means":
+                raise ValueError("bnn_predict: means is required")
+            continue
+        if out.dtype != dt:
+            raise TypeError("bnn_predict: %s must be %s" % (name, dt))
+        if out.numel() != numel or out.device != first.device:
+            raise ValueError("bnn_predict: %s must hold %d elements on %s" % (name, numel, first.device))
+    if (ens_mean is None) != (ens_var is None):
+        raise ValueError("bnn_predict: ens_mean and ens_var go together")
+    table = (ctypes.c_void_p * len(mats))(*[x.data_ptr() for x in mats])
+    with torch.cuda.device(first.device):
+        rc = f(table, len(mats), n, ld, (ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, _ptr(X), N, _ptr(means),
+               _ptr(noise_var), _ptr(ens_mean), _ptr(ens_var), _stream(first))
+    check(rc, "sgmcmc_bnn_predict")
+    return means
 
 
 def summary_workspace(device):

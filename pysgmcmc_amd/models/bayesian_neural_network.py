@@ -824,6 +824,7 @@ class BayesianNeuralNetwork(object):
         self.n_chains = n_chains
         self.chains = None
         self.is_trained = False
+        self._kept_matrix = None                 # predict(on_device=True): the kept networks as one (n_kept, P) device matrix
         # use the analytic-backward cost path (gradients straight into the arena)
         self.fused_cost = True
         # replay the ~25 launches of the cost/gradient pipeline from one hipGraph per step; the 3x50
@@ -926,6 +927,7 @@ class BayesianNeuralNetwork(object):
         self._adopt_data(X, y, device)
         self._build_sampler(X.shape[0], X.shape[1], device)
         self.samples.clear()
+        self._kept_matrix = None
         fused = bool(self.use_fused_steps and self.fused_cost and hasattr(self.sampler, "fused_bnn_available")
                      and self.sampler.fused_bnn_available())
         self.used_fused_steps = fused
@@ -1026,10 +1028,42 @@ class BayesianNeuralNetwork(object):
             out[:, :, 1:2] = log_var
         return out.cpu().numpy()
 
-    def predict(self, X_test, return_individual_predictions=False, *args, **kwargs):
+    def _kept_networks_matrix(self):
+        """The kept networks as ONE ``(n_kept, P)`` device matrix of flat parameter vectors (``W1, b1, ..., log_var``, the
+        whole-step kernel's order) and their layer sizes; flattened once and kept until ``train`` runs again."""
+        nets = list(self.samples)
+        if self._kept_matrix is None or self._kept_matrix[0].shape[0] != len(nets):
+            first = nets[0][0]
+            dev = first.device if isinstance(first, torch.Tensor) else self._device()
+            as_t = lambda p: torch.as_tensor(p, dtype=self._torch_dtype, device=dev)
+            n_layers = (len(nets[0]) - 1) // 2
+            sizes = [int(nets[0][0].shape[0])] + [int(nets[0][2 * l].shape[1]) for l in range(n_layers)]
+            flat = torch.stack([torch.cat([as_t(p).reshape(-1) for p in net]) for net in nets])
+            self._kept_matrix = (flat, sizes)
+        return self._kept_matrix
+
+    def _predict_on_device(self, x, return_individual_predictions):
+        """``predict``'s normalised moments from K11 (``models.posterior_predictive``) as host arrays: ``(means,
+        noise_var)``, both ``(n_nets, N)``, or ``(ensemble_mean, ensemble_var)``."""
+        from pysgmcmc_amd.models.predictive import posterior_predictive
+        flat, sizes = self._kept_networks_matrix()
+        xd = torch.as_tensor(np.ascontiguousarray(x), dtype=self._torch_dtype, device=flat.device)
+        a, b = posterior_predictive(flat, xd, sizes, return_individual_predictions=return_individual_predictions)
+        a, b = a.cpu().numpy(), b.cpu().numpy()
+        if return_individual_predictions:
+            b = np.repeat(b[:, None], a.shape[1], axis=1)
+        return a, b
+
+    def predict(self, X_test, return_individual_predictions=False, *args, on_device=False, **kwargs):
         """Predictive mean and variance at ``X_test (N, D)`` (``:560-630``): the kept networks' means and noise
         variances ``(n_nets, N)`` if ``return_individual_predictions``, else the ensemble mean and the variance of the
-        networks' means."""
+        networks' means.
+
+        ``on_device=True`` (extension): the kept networks go through the posterior-predictive kernel K11
+        (``models.posterior_predictive``) as one device matrix instead of batched products with activations in HBM and a host
+        reduction; the ensemble moments are then reduced in float64 on the device. The normalisation of ``X_test`` and of the
+        outputs stays the host code below; the return types are the same. A net the kernel refuses raises the library's
+        error (no fallback)."""
         assert X_test.ndim == 2
         if not self.is_trained:
             raise ValueError(
@@ -1038,15 +1072,23 @@ class BayesianNeuralNetwork(object):
                 "Please call `bnn.train()` before calling `bnn.predict()`"
             )
         x = zero_mean_unit_var_normalization(X_test, self.x_mean, self.x_std)[0] if self.normalize_input else X_test
-        outputs = self._network_outputs(x)                                   # (nets, N, 2)
-        means, noise_var = outputs[:, :, 0], np.exp(outputs[:, :, 1])
+        if on_device:
+            first, second = self._predict_on_device(x, return_individual_predictions)
+            if return_individual_predictions:
+                means, noise_var = first, second
+            else:
+                ensemble_mean, ensemble_var = first, second
+        else:
+            outputs = self._network_outputs(x)                               # (nets, N, 2)
+            means, noise_var = outputs[:, :, 0], np.exp(outputs[:, :, 1])
         if return_individual_predictions:
             if self.normalize_output:
                 means = zero_mean_unit_var_unnormalization(means, self.y_mean, self.y_std)
                 noise_var = noise_var * self.y_std ** 2
             return means, noise_var
-        ensemble_mean = means.mean(axis=0)
-        ensemble_var = ((means - ensemble_mean) ** 2).mean(axis=0)
+        if not on_device:
+            ensemble_mean = means.mean(axis=0)
+            ensemble_var = ((means - ensemble_mean) ** 2).mean(axis=0)
         if self.normalize_output:
             ensemble_mean = zero_mean_unit_var_unnormalization(ensemble_mean, self.y_mean, self.y_std)
             ensemble_var = ensemble_var * self.y_std ** 2

@@ -1,0 +1,68 @@
+"""Posterior predictive of a small tanh-MLP BNN from device-resident traces, in one device call.
+
+The reference's ``predict`` (``pysgmcmc/models/bayesian_neural_network.py:560-630``) evaluates the kept networks one by one
+and reduces on the host. Here the samples stay where ``FusedBNNChains.collect`` / ``DeviceTrace.record`` left them:
+``posterior_predictive`` hands the trace to K11 (``kernels.bnn_predict``, ``include/sgmcmc_hip_predict.h``), which runs every
+sampled network at every test row out of the LDS and reduces over the samples on the device. Nothing here waits for the host.
+"""
+import torch
+
+from pysgmcmc_amd import kernels
+from pysgmcmc_amd.diagnostics.device_trace import _chain_matrices
+
+__all__ = ["posterior_predictive"]
+
+
+def posterior_predictive(traces, X, layer_sizes, return_individual_predictions=False):
+    """Predictive moments at the rows of ``X`` of the networks sampled in ``traces``.
+
+    ``traces``: what ``diagnostics.effective_n_all`` accepts -- a ``DeviceTrace``, a sequence of them (at most 64), or a
+    device tensor ``(n, P)`` / ``(m, n, P)`` -- whose rows are flat parameter vectors in the whole-step kernel's order
+    (``W1, b1, ..., WL, bL, log_var``). A 3-D tensor whose chains lie back to back goes down as one matrix, whatever ``m``.
+    ``X``: contiguous ``(N, layer_sizes[0])`` device tensor of the traces' dtype, already normalised. ``layer_sizes``: ``[inputs,
+    hidden..., 1]``, 1 to 8 weight layers.
+
+    Returns device tensors, ``S`` = the number of samples: by default ``(ens_mean, ens_var)``, float64 ``(N,)``, the mean
+    over the samples of the networks' outputs and their population variance; with ``return_individual_predictions``
+    ``(means, noise_var)`` of the traces' dtype, ``(S, N)`` and ``(S,)``: every network's output at every row and its
+    ``exp(log_var)``. Allocates its outputs and nothing else. ``ValueError`` / ``TypeError`` for traces on the host, of
+    mismatched widths, narrower than the layer sizes need, or an ``X`` that does not fit them; a net the kernel refuses
+    (its parameters do not fit the LDS) raises ``SgmcmcLibraryError``."""
+    chains = traces
+    if not (torch.is_tensor(traces) and traces.dim() == 3):
+        chains = _chain_matrices(traces)
+        if len(chains) > 64:
+            raise ValueError("posterior_predictive: at most 64 separate chains, got %d (stack them into one (m, n, P) "
+                             "tensor)" % len(chains))
+    mats = [chains] if torch.is_tensor(chains) else chains
+    first = mats[0]
+    sizes = [int(v) for v in layer_sizes]
+    if len(sizes) < 2:
+        raise ValueError("posterior_predictive: layer_sizes must name the inputs and at least one layer")
+    n_params = kernels._bnn_n_params(sizes)
+    if int(first.shape[-1]) < n_params:
+        raise ValueError("posterior_predictive: the traces are %d wide, layer sizes %s need %d parameters" % (
+            first.shape[-1], sizes, n_params))
+    if not torch.is_tensor(X) or X.dim() != 2 or int(X.shape[1]) != sizes[0]:
+        raise ValueError("posterior_predictive: X must be an (N, %d) tensor, got %s" % (
+            sizes[0], tuple(X.shape) if torch.is_tensor(X) else type(X).__name__))
+    for x in mats:
+        if not x.is_cuda:
+            raise TypeError("posterior_predictive: the traces live on %s; they must be device tensors" % x.device)
+        if x.dtype != first.dtype or x.device != first.device:
+            raise TypeError("posterior_predictive: the traces must share a dtype and a device")
+    if X.dtype != first.dtype or X.device != first.device:
+        raise TypeError("posterior_predictive: X must be a %s tensor on %s" % (first.dtype, first.device))
+    S = first.shape[0] * first.shape[1] if first.dim() == 3 else len(mats) * first.shape[0]
+    if int(S) == 0:
+        raise ValueError("posterior_predictive: the traces hold no samples")
+    N, dev = int(X.shape[0]), first.device
+    means = torch.empty(int(S), N, dtype=first.dtype, device=dev)
+    if return_individual_predictions:
+        noise_var = torch.empty(int(S), dtype=first.dtype, device=dev)
+        kernels.bnn_predict(chains, sizes, X, means, noise_var=noise_var)
+        return means, noise_var
+    ens_mean = torch.empty(N, dtype=torch.float64, device=dev)
+    ens_var = torch.empty(N, dtype=torch.float64, device=dev)
+    kernels.bnn_predict(chains, sizes, X, means, ens_mean=ens_mean, ens_var=ens_var)
+    return ens_mean, ens_var

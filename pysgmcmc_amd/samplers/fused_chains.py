@@ -116,6 +116,18 @@ class FusedBNNChains(object):
             self.steps(n_samples * every, trace=out, keep_every=every)
         return out
 
+    def predict(self, X, trace, **kw):
+        """Posterior predictive of the samples in ``trace`` (what :meth:`collect` returns, or anything
+        ``models.posterior_predictive`` accepts) at the rows of ``X``, with the group's own layer sizes, in one device
+        call: ``chains.collect(n, every)`` -> ``effective_n_all(t)`` -> ``chains.predict(X, t)`` is three launches and
+        no host copy of a parameter. ``X``: a device tensor of the chains' dtype, or an array that is uploaded; already
+        normalised. Returns device tensors: ``(ens_mean, ens_var)``, or ``(means, noise_var)`` with
+        ``return_individual_predictions=True``."""
+        from pysgmcmc_amd.models.predictive import posterior_predictive
+        if not torch.is_tensor(X):
+            X = torch.as_tensor(np.asarray(X), dtype=self.storage.dtype, device=self.storage.device)
+        return posterior_predictive(trace, X, self.samplers[0]._bnn_layer_sizes(), **kw)
+
     @classmethod
     def for_dataset(cls, X, y, n_chains, hidden=(50, 50, 50), batch_size=20, seed=0, dtype=torch.float32,
                     device="cuda:0", stepsize=0.01, burn_in_steps=1000, mdecay=0.05, init_seed=None):

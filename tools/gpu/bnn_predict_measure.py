@@ -1,0 +1,88 @@
+"""Times ``models.posterior_predictive`` (K11, include/sgmcmc_hip_predict.h) against ``BayesianNeuralNetwork.predict``'s host
+path (batched products with activations in HBM, one copy to the host, numpy reduction) on the same kept networks: 100
+networks x 1 000 rows in f32 and f64, and a (256, 100, 5252) f32 trace x 1 000 rows. Medians of 11 runs after a warm-up
+call: device events on the stream for the device call, a host clock around calls that end in a device-to-host copy.
+The record is profiles/bnn_predict.txt.
+
+    python tools/gpu/bnn_predict_measure.py [output file]
+"""
+import os, sys, time, statistics
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import numpy as np
+import torch
+from pysgmcmc_amd import kernels
+from pysgmcmc_amd.models import BayesianNeuralNetwork, posterior_predictive
+from pysgmcmc_amd.models.bayesian_neural_network import init_mlp_params
+
+out = open(sys.argv[1], "w") if len(sys.argv) > 1 else open(os.devnull, "w")
+def say(*a):
+    line = " ".join(str(x) for x in a)
+    print(line, flush=True); out.write(line + "\n"); out.flush()
+
+dev = torch.device("cuda:0")
+sizes = [1, 50, 50, 50, 1]
+P = 5252
+shapes = [(1, 50), (50,), (50, 50), (50,), (50, 50), (50,), (50, 1), (1,), (1, 1)]
+say("device", torch.cuda.get_device_name(0), "torch", torch.__version__)
+say("row tile f32", kernels.bnn_predict_row_tile(sizes, torch.float32), "f64", kernels.bnn_predict_row_tile(sizes, torch.float64))
+
+def trace(m, n, dt):
+    g = torch.Generator(device="cpu").manual_seed(7)
+    base = torch.cat([p.reshape(-1) for p in init_mlp_params(1, seed=5)])
+    t = base[None, None, :] + 0.1 * torch.randn(m, n, P, generator=g, dtype=torch.float64)
+    t[:, :, -1] = np.log(1e-3) + 0.01 * torch.rand(m, n, generator=g, dtype=torch.float64)
+    return t.to(dt).to(dev)
+
+def nets_of(flat):
+    nets = []
+    for s in range(flat.shape[0]):
+        row, off, net = flat[s], 0, []
+        for shp in shapes:
+            k = int(np.prod(shp)); net.append(row[off:off + k].view(shp)); off += k
+        nets.append(net)
+    return nets
+
+def events(fn, runs=11):
+    fn(); torch.cuda.synchronize()
+    ts = []
+    for _ in range(runs):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record(); b.synchronize(); ts.append(a.elapsed_time(b))
+    return statistics.median(ts), min(ts), max(ts)
+
+def wall(fn, runs=11, budget=150.0):
+    t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize(); first = time.perf_counter() - t0
+    ts = []
+    for _ in range(runs):
+        if ts and sum(ts) + first > budget: break
+        torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
+    return statistics.median(ts) * 1e3, min(ts) * 1e3, max(ts) * 1e3, len(ts), r
+
+X = np.random.RandomState(0).uniform(-1, 1, size=(1000, 1))
+for dt in (torch.float32, torch.float64):
+    for (m, n) in ((1, 100), (256, 100)):
+        S = m * n
+        if dt == torch.float64 and S > 100:
+            continue
+        t = trace(m, n, dt)
+        Xd = torch.as_tensor(X, dtype=dt, device=dev)
+        say("---- %d networks x 1000 rows, %s" % (S, dt))
+        med, lo, hi = events(lambda: posterior_predictive(t, Xd, sizes))
+        say("posterior_predictive (ens_mean, ens_var), device events: median %.3f ms (min %.3f, max %.3f) of 11" % (med, lo, hi))
+        med, lo, hi = events(lambda: posterior_predictive(t, Xd, sizes, return_individual_predictions=True))
+        say("posterior_predictive (means, noise_var), device events:  median %.3f ms (min %.3f, max %.3f) of 11" % (med, lo, hi))
+        bnn = BayesianNeuralNetwork(session=dev, dtype=dt, n_nets=S, normalize_input=False, normalize_output=False)
+        bnn.is_trained = True
+        t0 = time.perf_counter()
+        bnn.samples.extend(nets_of(t.view(S, P)))
+        say("cut into %d kept networks (host): %.2f s" % (S, time.perf_counter() - t0))
+        med, lo, hi, k, dev_out = wall(lambda: bnn.predict(X, on_device=True))
+        say("predict(on_device=True) to numpy, host clock:  median %.3f ms (min %.3f, max %.3f) of %d" % (med, lo, hi, k))
+        runs = 11 if S <= 100 else 3
+        med, lo, hi, k, host_out = wall(lambda: bnn.predict(X), runs=runs)
+        say("predict() host path to numpy, host clock:      median %.3f ms (min %.3f, max %.3f) of %d" % (med, lo, hi, k))
+        say("max |ensemble mean difference| %.3e, max |ensemble variance difference| %.3e (max |mean| %.3e)" % (
+            np.abs(dev_out[0] - host_out[0]).max(), np.abs(dev_out[1] - host_out[1]).max(), np.abs(host_out[0]).max()))
+        del bnn, t
+        torch.cuda.empty_cache()
+say("done")
