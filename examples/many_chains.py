@@ -1,5 +1,6 @@
 """256 SGHMC chains of the reference's default BNN advanced together (one workgroup per chain), then the
-Gelman-Rubin statistic across them -- the job `pysgmcmc/diagnostics/sample_chains.py` does chain after chain."""
+Gelman-Rubin statistic and the effective sample size of EVERY parameter across ALL of them in one more launch -- the job
+`pysgmcmc/diagnostics/sample_chains.py` and `sampler_diagnostics.py` do chain after chain and dimension after dimension."""
 import os
 import sys
 
@@ -10,8 +11,6 @@ import time
 import numpy as np
 import torch
 
-from pysgmcmc_amd.diagnostics.device_trace import effective_n_all
-from pysgmcmc_amd.diagnostics.sampler_diagnostics import gelman_rubin_from_chains
 from pysgmcmc_amd.samplers.fused_chains import FusedBNNChains
 
 rng = np.random.RandomState(1)
@@ -24,9 +23,11 @@ chains.steps(5000)                                       # burn-in and mixing
 snaps = chains.collect(50, every=100)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
-# R-hat of the network's prediction at x = 0.5 is more telling than of single weights (weight-space symmetries)
-rhat = gelman_rubin_from_chains(snaps[:, :, -1:])        # the log-variance parameter
-print("%d chains x %d steps in %.2f s = %.2f M samples/s; R-hat of the noise log-variance: %.3f"
-      % (chains.n_chains, chains.n_iterations, dt, chains.n_chains * chains.n_iterations / dt / 1e6, float(rhat)))
-ess = effective_n_all(snaps[:64])                        # every parameter's ESS over 64 of the chains, one more launch
-print("effective sample size of %d parameters: median %d of %d kept samples" % (ess.numel(), int(ess.median()), 64 * 50))
+print("%d chains x %d steps in %.2f s = %.2f M samples/s"
+      % (chains.n_chains, chains.n_iterations, dt, chains.n_chains * chains.n_iterations / dt / 1e6))
+# R-hat and ESS of all 5252 parameters over all 256 chains, on the device. R-hat of single weights is a stern judge (the
+# weight-space symmetries of an MLP keep chains apart that predict alike); the last parameter is the noise log-variance.
+rhat, ess = chains.diagnose(snaps)
+print("R-hat of %d parameters over %d chains: max %.3f, median %.3f; of the noise log-variance: %.3f"
+      % (rhat.numel(), chains.n_chains, float(rhat.max()), float(rhat.median()), float(rhat[-1])))
+print("effective sample size: median %d of %d kept samples" % (int(ess.median()), snaps.shape[0] * snaps.shape[1]))

@@ -49,9 +49,11 @@ DIAG_ABI_VERSION = 1          # SGMCMC_DIAG_ABI_VERSION of include/sgmcmc_hip_di
 FUSED_ABI_VERSION = 1         # SGMCMC_FUSED_ABI_VERSION of include/sgmcmc_hip_fused.h (the whole-step add-on)
 FUSED_TRACE_ABI_VERSION = 1   # SGMCMC_FUSED_TRACE_ABI_VERSION of include/sgmcmc_hip_fused_trace.h (the thinned-trace add-on)
 PREDICT_ABI_VERSION = 1       # SGMCMC_PREDICT_ABI_VERSION of include/sgmcmc_hip_predict.h (the posterior-predictive add-on)
+CHAINS_ABI_VERSION = 1        # SGMCMC_CHAINS_ABI_VERSION of include/sgmcmc_hip_chains.h (the many-chains diagnostics add-on)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
+CHAINS_MAX_CHAINS = 4096
 
 _u64 = ctypes.c_uint64
 _sz = ctypes.c_size_t
@@ -231,6 +233,12 @@ def _declare(lib):
         f.restype = _ci
     lib.sgmcmc_bnn_predict_row_tile.argtypes = [ctypes.POINTER(_ci), _ci, _sz]
     lib.sgmcmc_bnn_predict_row_tile.restype = _ci
+    # include/sgmcmc_hip_chains.h: trace, m, n, P, ld, chain_stride, rhat, ess, raw, stop_lag, waves, stream
+    lib.sgmcmc_chains_abi_version.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_chain_diag_" + sfx)
+        f.argtypes = [_vp, _ci, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _ci, _vp]
+        f.restype = _ci
 
 
 def lib():
@@ -257,6 +265,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: thinned-trace add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_predict_abi_version() != PREDICT_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: posterior-predictive add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_chains_abi_version() != CHAINS_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: many-chains diagnostics add-on (chains ABI) version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

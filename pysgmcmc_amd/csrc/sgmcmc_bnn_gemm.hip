@@ -41,7 +41,6 @@
 // fp32 MFMA is an exact fmaf chain (MI355X_MICROARCH.md): the product differs from a library GEMM in summation order only.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <type_traits>
@@ -457,21 +456,8 @@ struct ColumnPlan {
     int parts;                  // column tiles in all = rows of dot_parts: n_full / 64 + (N - n_full) / 32
 };
 
-// Compute units of the current device, queried once per device and kept (the plan a caller sized dot_parts with and the plan a
-// launch uses must be the same split: both read this). 0: no device / the query failed.
-int current_device_cus()
-{
-    constexpr int MAX_DEV = 64;
-    static std::atomic<int> cached[MAX_DEV];                // zero-initialised: 0 = not asked yet
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return 0;
-    int cus = cached[dev].load(std::memory_order_relaxed);
-    if (cus > 0) return cus;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
-    cached[dev].store(cus, std::memory_order_relaxed);
-    return cus;
-}
-
+// current_device_cus() (sgmcmc_host.hpp): the plan a caller sized dot_parts with and the plan a launch uses must be the same
+// split, and both read that one cached count.
 ColumnPlan plan_columns(int M, int N, int cus)
 {
     const int tiles_m = M / BM, col_tiles = N / 64, tiles = tiles_m * col_tiles;

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstddef>
 #include <cstdio>
 
@@ -28,5 +29,19 @@ inline unsigned small_grid(size_t n)
     size_t want = (n + 255) / 256;
     size_t cap = (size_t)1 << 20;
     return (unsigned)(want < cap ? (want ? want : 1) : cap);
+}
+
+// Compute units of the current device, queried once per device and kept. 0: no device / the query failed.
+inline int current_device_cus()
+{
+    constexpr int MAX_DEV = 64;
+    static std::atomic<int> cached[MAX_DEV];                // zero-initialised: 0 = not asked yet
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return 0;
+    int cus = cached[dev].load(std::memory_order_relaxed);
+    if (cus > 0) return cus;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
+    cached[dev].store(cus, std::memory_order_relaxed);
+    return cus;
 }
 }  // namespace sgmcmc_host

@@ -1,8 +1,10 @@
 """Diagnostics: toy targets, trace containers and cross-chain statistics (same exports as
-``pysgmcmc/diagnostics/__init__.py:1-9``), plus the device-resident trace and the all-parameter effective sample size."""
-from pysgmcmc_amd.diagnostics.device_trace import DeviceTrace, effective_n_all, effective_sample_sizes_of
+``pysgmcmc/diagnostics/__init__.py:1-9``), plus the device-resident trace, the all-parameter effective sample size and the
+all-parameter R-hat and ESS of many chains."""
+from pysgmcmc_amd.diagnostics.device_trace import (DeviceTrace, chain_diagnostics_all, effective_n_all,
+                                                    effective_sample_sizes_of, gelman_rubin_all)
 from pysgmcmc_amd.diagnostics.sample_chains import PYSGMCMCTrace, pymc3_multitrace
 from pysgmcmc_amd.diagnostics.sampler_diagnostics import effective_sample_sizes, gelman_rubin
 
 __all__ = ("PYSGMCMCTrace", "pymc3_multitrace", "effective_sample_sizes", "gelman_rubin",
-           "DeviceTrace", "effective_n_all", "effective_sample_sizes_of")
+           "DeviceTrace", "effective_n_all", "effective_sample_sizes_of", "chain_diagnostics_all", "gelman_rubin_all")

@@ -10,6 +10,9 @@ its estimator for ONE scalar (an FFT and a host read per call). Here the trace n
                                   (``sampler.fused_bnn_steps(n, trace, keep_every)``)
   ``effective_n_all``             one launch of K10 (``kernels.ess_variogram``) -> int64 ESS of all P parameters, on the
                                   device, no host synchronisation
+  ``chain_diagnostics_all``       one launch of K12 (``kernels.chain_diag``) -> float64 R-hat AND int64 ESS of all P
+                                  parameters from up to 4096 chains (K10 stops at 64); ``gelman_rubin_all`` is its
+                                  R-hat-only launch
   ``effective_sample_sizes_of``   the reference's ``{name: array shaped like the parameter}`` cut from that vector
 
 Scope: chains that share a device (``ConcurrentChains``, sequential chains as in ``multitrace``, the stacked state of
@@ -21,7 +24,7 @@ import torch
 
 from pysgmcmc_amd import kernels
 
-__all__ = ["DeviceTrace", "effective_n_all", "effective_sample_sizes_of"]
+__all__ = ["DeviceTrace", "effective_n_all", "effective_sample_sizes_of", "chain_diagnostics_all", "gelman_rubin_all"]
 
 
 class DeviceTrace(object):
@@ -131,8 +134,8 @@ class DeviceTrace(object):
         return trace
 
 
-def _chain_matrices(traces):
-    """``traces`` of effective_n_all -> list of (n, P) tensors, one per chain."""
+def _chain_matrices(traces, who="effective_n_all"):
+    """``traces`` of effective_n_all (or of ``who``) -> list of (n, P) tensors, one per chain."""
     if isinstance(traces, DeviceTrace):
         return [traces.values()]
     if torch.is_tensor(traces):
@@ -140,13 +143,13 @@ def _chain_matrices(traces):
             return [traces]
         if traces.dim() == 3:
             return list(traces.unbind(0))
-        raise ValueError("effective_n_all: a tensor of traces must be (n, P) or (m, n, P), got %s" % (tuple(traces.shape),))
+        raise ValueError("%s: a tensor of traces must be (n, P) or (m, n, P), got %s" % (who, tuple(traces.shape),))
     try:
         items = list(traces)
     except TypeError:
-        raise TypeError("effective_n_all: traces must be a DeviceTrace, a sequence of them or a device tensor")
+        raise TypeError("%s: traces must be a DeviceTrace, a sequence of them or a device tensor" % who)
     if not items:
-        raise ValueError("effective_n_all: no traces")
+        raise ValueError("%s: no traces" % who)
     mats = []
     for t in items:
         if isinstance(t, DeviceTrace):
@@ -154,13 +157,13 @@ def _chain_matrices(traces):
         elif torch.is_tensor(t) and t.dim() == 2:
             mats.append(t)
         else:
-            raise TypeError("effective_n_all: every chain must be a DeviceTrace or an (n, P) tensor")
+            raise TypeError("%s: every chain must be a DeviceTrace or an (n, P) tensor" % who)
     first = mats[0]
     for x in mats[1:]:
         if x.shape[0] != first.shape[0]:
-            raise ValueError("effective_n_all: the chains hold different numbers of samples (%d and %d)" % (first.shape[0], x.shape[0]))
+            raise ValueError("%s: the chains hold different numbers of samples (%d and %d)" % (who, first.shape[0], x.shape[0]))
         if x.shape[1] != first.shape[1]:
-            raise ValueError("effective_n_all: the chains are of different widths (%d and %d)" % (first.shape[1], x.shape[1]))
+            raise ValueError("%s: the chains are of different widths (%d and %d)" % (who, first.shape[1], x.shape[1]))
     return mats
 
 
@@ -186,6 +189,56 @@ def effective_n_all(traces, details=False, staging="auto", launch=None):
     stop = torch.empty(P, dtype=torch.int32, device=dev) if details else None
     kernels.ess_variogram(mats, ess, raw, stop, staging=staging, launch=launch)
     return (ess, raw, stop) if details else ess
+
+
+def _stacked_trace(traces, who):
+    """``traces`` of chain_diagnostics_all -> one (m, n, P) tensor: a tensor goes through as it is, a sequence is stacked."""
+    mats = None if torch.is_tensor(traces) and traces.dim() == 3 else _chain_matrices(traces, who)
+    m, n = (traces.shape[0], traces.shape[1]) if mats is None else (len(mats), mats[0].shape[0])
+    if m < 1:
+        raise ValueError("%s: no traces" % who)
+    if n < 2:
+        raise ValueError("%s: needs at least 2 samples per chain, got %d" % (who, n))
+    if m > 4096:
+        raise ValueError("%s: at most 4096 chains, got %d" % (who, m))
+    if mats is None:
+        return traces
+    return mats[0].unsqueeze(0) if m == 1 else torch.stack(mats)
+
+
+def gelman_rubin_all(traces):
+    """Gelman-Rubin R-hat of each of the P parameters, ``sqrt(Vhat / W)``, as a float64 ``(P,)`` device tensor: the
+    R-hat-only launch of K12 (``kernels.chain_diag``), which takes the chain moments and walks no lag. ``traces`` as for
+    :func:`chain_diagnostics_all`. NaN where a parameter's ``Vhat`` is zero or not finite, ``+inf`` where every chain is
+    constant at a value of its own; with ONE chain the formula gives ``sqrt((n - 1) / n)``. Nothing waits for the host."""
+    x = _stacked_trace(traces, "gelman_rubin_all")
+    rhat = torch.empty(int(x.shape[2]), dtype=torch.float64, device=x.device)
+    kernels.chain_diag(x, rhat=rhat)
+    return rhat
+
+
+def chain_diagnostics_all(traces, details=False):
+    """R-hat and effective sample size of each of the P parameters across up to 4096 chains, in ONE launch of K12
+    (``kernels.chain_diag``) on the traces' device: ``(rhat, ess)``, float64 and int64 ``(P,)`` device tensors; with
+    ``details=True`` ``(rhat, ess, raw, stop_lag)`` as :func:`effective_n_all` gives them.
+
+    ``traces``: what :func:`effective_n_all` accepts. A device tensor ``(m, n, P)`` (what ``FusedBNNChains.collect``
+    returns, or a view of a wider or longer buffer with dense rows) goes down as it is, without a copy and with any
+    ``m <= 4096``; an ``(n, P)`` tensor or a ``DeviceTrace`` is one chain; a sequence of ``DeviceTrace``s or matrices that
+    live in buffers of their own is stacked into one ``(m, n, P)`` tensor first -- that ONE device copy is the price of
+    the kernel's single base pointer (K10, ``effective_n_all``, takes up to 64 separate buffers without it). At least 2
+    samples per chain. The estimators are those of ``effective_n_all`` and ``gelman_rubin``; for up to 16 chains ``ess``,
+    ``raw`` and ``stop_lag`` equal ``effective_n_all``'s bit for bit, beyond that the chains are summed in groups of 16
+    (``include/sgmcmc_hip_chains.h``). Degenerate parameters: ``rhat`` NaN, ``ess`` 0, ``raw`` NaN, ``stop_lag`` 1.
+    Nothing here waits for the host. Chains on different ranks are out of scope (see the module docstring)."""
+    x = _stacked_trace(traces, "chain_diagnostics_all")
+    P, dev = int(x.shape[2]), x.device
+    rhat = torch.empty(P, dtype=torch.float64, device=dev)
+    ess = torch.empty(P, dtype=torch.int64, device=dev)
+    raw = torch.empty(P, dtype=torch.float64, device=dev) if details else None
+    stop = torch.empty(P, dtype=torch.int32, device=dev) if details else None
+    kernels.chain_diag(x, rhat, ess, raw, stop)
+    return (rhat, ess, raw, stop) if details else (rhat, ess)
 
 
 def effective_sample_sizes_of(samplers_or_traces, param_shapes=None, names=None):

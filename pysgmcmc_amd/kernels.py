@@ -17,7 +17,7 @@ __all__ = [
     "moments_update", "rhat_pack", "rhat_finish", "summary",
     "LaunchConfig", "KernelEvents", "StepOpts", "step_stats_records", "step_scalars", "toy_chains", "set_launch_config", "get_launch_config", "summary_workspace", "counter_add", "StepStats", "bnn_head", "bnn_dense_tanh_backward", "bnn_dense_tanh_backward_fits", "colsum_finish", "tanh_backward", "tanh_backward_colsum", "bnn_last_layer_backward", "bnn_fused_sghmc_steps", "step_stats_finish",
     "bnn_fused_sgld_steps", "bnn_fused_rsghmc_steps", "bnn_fused_steps", "step_scalars_table", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
-    "ess_variogram", "bnn_predict", "bnn_predict_row_tile",
+    "ess_variogram", "bnn_predict", "bnn_predict_row_tile", "chain_diag",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -461,6 +461,51 @@ def ess_variogram(chains, ess, raw=None, stop_lag=None, ld=None, staging="auto",
         rc = f(table, len(mats), n, P, ld, _ptr(ess), _ptr(raw), _ptr(stop_lag), stage, _launch(launch), _stream(first))
     check(rc, "sgmcmc_ess_variogram")
     return ess
+
+
+def chain_diag(trace, rhat=None, ess=None, raw=None, stop_lag=None, waves=None):
+    """K12 (``include/sgmcmc_hip_chains.h``): R-hat and the effective sample size of every parameter from ONE strided
+    trace of up to 4096 chains, in one launch.
+
+    ``trace``: an ``(m, n, P)`` device tensor, or ``(n, P)`` for a single chain. Rows must be dense (stride 1 along P);
+    ``ld = stride(1)`` and ``chain_stride = stride(0)``, so views of wider or longer buffers pass without a copy.
+    ``rhat``: float64[P] or None; ``ess``: int64[P] or None; ``raw``: float64[P] or None; ``stop_lag``: int32[P] or None;
+    at least one of the four. With ``ess``, ``raw`` and ``stop_lag`` all None the launch takes the moments only (R-hat).
+    ``waves``: None (auto) or 1, 2, 4, 8, 16, the waves of a workgroup that share a parameter's chains (same bits).
+    Returns ``(rhat, ess, raw, stop_lag)`` as passed."""
+    if not torch.is_tensor(trace):
+        raise TypeError("chain_diag: trace must be an (m, n, P) or (n, P) device tensor")
+    if trace.dim() == 2:
+        trace = trace.unsqueeze(0)
+    if trace.dim() != 3:
+        raise ValueError("chain_diag: trace must be (m, n, P) or (n, P), got %s" % (tuple(trace.shape),))
+    if not trace.is_cuda:
+        raise SgmcmcLibraryError("pysgmcmc_amd: trace lives on %s; the chain diagnostics of all parameters run only as a "
+                                 "HIP kernel on an AMD GPU (no CPU fallback)." % trace.device)
+    f = getattr(lib(), "sgmcmc_chain_diag_" + _sfx(trace))
+    m, n, P = (int(v) for v in trace.shape)
+    if P > 1 and trace.stride(2) != 1:
+        raise ValueError("chain_diag: rows must be dense (stride 1 along the parameters)")
+    ld = int(trace.stride(1)) if n > 1 else P
+    chain_stride = int(trace.stride(0)) if m > 1 else max((n - 1) * ld + P, 0)
+    if ld < 0 or chain_stride < 0:
+        raise ValueError("chain_diag: negative strides are not supported")
+    outs = ((rhat, torch.float64, "rhat"), (ess, torch.int64, "ess"), (raw, torch.float64, "raw"),
+            (stop_lag, torch.int32, "stop_lag"))
+    if all(out is None for out, _, _ in outs):
+        raise ValueError("chain_diag: at least one of rhat, ess, raw and stop_lag is required")
+    for out, dt, name in outs:
+        if out is None:
+            continue
+        if out.dtype != dt:
+            raise TypeError("chain_diag: %s must be %s" % (name, dt))
+        if out.numel() != P or out.device != trace.device:
+            raise ValueError("chain_diag: %s must hold P = %d elements on %s" % (name, P, trace.device))
+    with torch.cuda.device(trace.device):
+        rc = f(trace.data_ptr(), m, n, P, ld, chain_stride, _ptr(rhat), _ptr(ess), _ptr(raw), _ptr(stop_lag),
+               0 if waves is None else int(waves), _stream(trace))
+    check(rc, "sgmcmc_chain_diag")
+    return rhat, ess, raw, stop_lag
 
 
 def _bnn_n_params(sizes):

@@ -107,8 +107,9 @@ class FusedBNNChains(object):
     def collect(self, n_samples, every=100):
         """``n_samples`` thinned snapshots of all chains: a ``[n_chains, n_samples, n_params]`` device tensor, written
         by ONE launch of ``n_samples * every`` steps that keeps every ``every``-th theta itself (no launch boundary and no
-        copy per snapshot), ready for ``diagnostics.device_trace.effective_n_all`` and
-        ``diagnostics.sampler_diagnostics.gelman_rubin_from_chains`` / ``effective_n``."""
+        copy per snapshot), ready for :meth:`diagnose` (R-hat and ESS of every parameter over ALL the chains) and
+        :meth:`predict`. ``diagnostics.device_trace.effective_n_all`` takes up to 64 of the chains (``t[:64]``);
+        ``diagnostics.sampler_diagnostics.gelman_rubin_from_chains`` works on a float64 copy, ``effective_n`` on one parameter."""
         n_samples, every = int(n_samples), int(every)
         a = self.samplers[0].arena
         out = torch.empty(self.n_chains, n_samples, a.n, dtype=self.storage.dtype, device=self.storage.device)
@@ -116,10 +117,17 @@ class FusedBNNChains(object):
             self.steps(n_samples * every, trace=out, keep_every=every)
         return out
 
+    def diagnose(self, trace, details=False):
+        """R-hat and effective sample size of every parameter over all the chains of ``trace`` (what :meth:`collect`
+        returns) in one device launch: ``diagnostics.chain_diagnostics_all(trace, details)`` -> ``(rhat, ess)``, or
+        ``(rhat, ess, raw, stop_lag)`` with ``details=True``. Nothing waits for the host."""
+        from pysgmcmc_amd.diagnostics.device_trace import chain_diagnostics_all
+        return chain_diagnostics_all(trace, details)
+
     def predict(self, X, trace, **kw):
         """Posterior predictive of the samples in ``trace`` (what :meth:`collect` returns, or anything
         ``models.posterior_predictive`` accepts) at the rows of ``X``, with the group's own layer sizes, in one device
-        call: ``chains.collect(n, every)`` -> ``effective_n_all(t)`` -> ``chains.predict(X, t)`` is three launches and
+        call: ``chains.collect(n, every)`` -> ``chains.diagnose(t)`` -> ``chains.predict(X, t)`` is three launches and
         no host copy of a parameter. ``X``: a device tensor of the chains' dtype, or an array that is uploaded; already
         normalised. Returns device tensors: ``(ens_mean, ens_var)``, or ``(means, noise_var)`` with
         ``return_individual_predictions=True``."""
