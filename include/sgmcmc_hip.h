@@ -541,6 +541,11 @@ int sgmcmc_window_gather_f64(const double *X, const double *y, size_t n_data, si
  * then `count` products C_z [nA][nB] (pitch ldc, overwritten) = sum_m A_z[m][:]^T B_z[m][:] run as ONE launch of six
  * v_mfma_f32_32x32x16_bf16 per 16 batch rows (the partial products of order <= 2^-16) with fp32 accumulation in a fixed order:
  * bit-reproducible, error against fp64 no larger than the library's fp32 product on the same operands (tests/test_bnn_dense_gpu.py).
+ * Domain of the split: x = (x0 + x1) + x2 holds exactly for 2^-110 <= |x| (up to the largest finite float) and for x = +-0.
+ * Plane 2 carries bits down to 2^-23 |x|, and bf16 denormals are multiples of 2^-133: for 0 < |x| < 2^-110 the planes add up
+ * to x less a remainder smaller than 2^-133. -0 keeps its sign in plane 0 only, (x0 + x1) + x2 returns +0. Inf and NaN are not
+ * specified. (tests/test_bnn_matrix_core_gpu.py pins the planes bit for bit on [2^-100, 2^100], at 2^-110, at +-0, and one value
+ * below the domain to its remainder.)
  *   sgmcmc_bnn_planes_bytes(M, N): bytes of one plane set (0: invalid shape; M % 16 == 0 required).
  *   split_planes: X_z = X + z * x_stride (elements) [M][ldx >= N] -> planes + z * planes_stride (bytes), z < count.
  *   gw_planes: plane sets a_planes + z * a_stride, b_planes + z * b_stride (bytes); C + z * c_stride (elements).

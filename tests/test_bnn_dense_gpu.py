@@ -10,16 +10,20 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-# (256, 4864, 4864): configs[4]'s hidden layer, 608 tiles = 2 rounds of full tiles + 192 HALF tiles on 256 compute units;
-# (512, 2048, 2048): two full rounds; (64, 144, 8704) / (32, 80, 8320): half tiles with K tails, XCD map on / off for the halves
+# On 256 compute units -- (256, 4864, 4864): configs[4]'s hidden layer, 608 tiles = 2 rounds of full tiles + 192 HALF tiles;
+# (512, 2048, 2048): two full rounds; (64, 144, 8704): 256 full tiles + 32 half tiles, K tail 16; (32, 80, 8320): 130 full tiles in
+# one round (no half tile), K tail 16, XCD map off. Both half-tile launches have the XCD map on (192 and 32 workgroups) and K
+# tail 0 or 16: half tiles with the map off, fewer than 8 of them, and the other K tails are in tests/test_bnn_matrix_core_gpu.py
 BIG_SHAPES = [(256, 4864, 4864), (512, 2048, 2048), (64, 144, 8704), (32, 80, 8320)]
 
 
 @pytest.mark.parametrize("M,K,N", [(256, 2048, 2048), (256, 784, 2048), (32, 64, 64), (64, 80, 128), (96, 272, 192), (32, 1040, 64)] + BIG_SHAPES)
 def test_dense_tanh_equals_an_fp64_product(gpu, M, K, N):
-    """Every K tail (K % 64 in {0, 16, 32, 48}), ragged tile counts (XCD map on and off), pitched operands, more tiles than compute
-    units (rounds of workgroups, a thin last round as half tiles); the output unit's partial dot products add up to the GEMV;
-    two launches give the same bits (no atomics, fixed summation order)."""
+    """Gaussian operands at the shapes of the nets (K tails K % 64 of 0 and 16, chunk counts 1, 2, 3, 5, 13, 17, 32, 76), ragged
+    tile counts (XCD map on and off), pitched operands, more tiles than compute units (rounds of workgroups, a thin last round as
+    half tiles); the output unit's partial dot products add up to the GEMV; two launches give the same bits (no atomics, fixed
+    summation order). Every K tail {0, 16, 32, 48} at every ring phase, on every tile kind and map, with exact operands:
+    tests/test_bnn_matrix_core_gpu.py."""
     from pysgmcmc_amd import kernels
     g = torch.Generator(device=gpu).manual_seed(M + K + N)
     hbuf = torch.randn(M, K + 8, device=gpu, generator=g)
@@ -33,7 +37,7 @@ def test_dense_tanh_equals_an_fp64_product(gpu, M, K, N):
     tiles = (M // 32) * (N // 64)
     if tiles <= cus or tiles % cus == 0:
         assert n_parts == N // 64
-    elif (M, N) in ((256, 4864), (64, 8704), (32, 8320)) and cus == 256:
+    elif (M, N) in ((256, 4864), (64, 8704)) and cus == 256:
         assert n_parts > N // 64                                 # the thin last round runs as half tiles
     parts = torch.zeros(n_parts, M, device=gpu)
     assert kernels.bnn_dense_tanh_fits(h, W, out[:M])
@@ -71,8 +75,9 @@ def test_dense_tanh_refuses_what_it_cannot_take(gpu):
 @pytest.mark.parametrize("M,K,N", [(256, 2048, 2048), (256, 2048, 784 + 48), (32, 64, 64), (64, 80, 128), (96, 272, 192), (32, 1040, 64),
                                    (160, 64, 320)] + BIG_SHAPES)
 def test_dense_tanh_backward_equals_an_fp64_product(gpu, M, K, N):
-    """out = (delta W^T) (1 - act^2) and its column sums per 32-row tile: every K tail, one and several row tiles, XCD map on and
-    off, pitched operands. The row tiles are added up -- in order -- by a small launch or by the NEXT backward launch on the
+    """out = (delta W^T) (1 - act^2) and its column sums per 32-row tile: Gaussian operands, K tails 0 and 16 (all four, at every
+    ring phase, with exact operands: tests/test_bnn_matrix_core_gpu.py), one and several row tiles, XCD map on and off,
+    pitched operands. The row tiles are added up -- in order -- by a small launch or by the NEXT backward launch on the
     side: same bits either way, and from launch to launch."""
     from pysgmcmc_amd import kernels
     g = torch.Generator(device=gpu).manual_seed(M + 3 * K + N)
