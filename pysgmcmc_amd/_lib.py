@@ -50,10 +50,12 @@ FUSED_ABI_VERSION = 1         # SGMCMC_FUSED_ABI_VERSION of include/sgmcmc_hip_f
 FUSED_TRACE_ABI_VERSION = 1   # SGMCMC_FUSED_TRACE_ABI_VERSION of include/sgmcmc_hip_fused_trace.h (the thinned-trace add-on)
 PREDICT_ABI_VERSION = 1       # SGMCMC_PREDICT_ABI_VERSION of include/sgmcmc_hip_predict.h (the posterior-predictive add-on)
 CHAINS_ABI_VERSION = 1        # SGMCMC_CHAINS_ABI_VERSION of include/sgmcmc_hip_chains.h (the many-chains diagnostics add-on)
+SCORE_ABI_VERSION = 1         # SGMCMC_SCORE_ABI_VERSION of include/sgmcmc_hip_score.h (the held-out-score add-on)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
 CHAINS_MAX_CHAINS = 4096
+SCORE_MAX_CHAINS = 64
 
 _u64 = ctypes.c_uint64
 _sz = ctypes.c_size_t
@@ -239,6 +241,13 @@ def _declare(lib):
         f = getattr(lib, "sgmcmc_chain_diag_" + sfx)
         f.argtypes = [_vp, _ci, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _ci, _vp]
         f.restype = _ci
+    # include/sgmcmc_hip_score.h: host array of chain matrices, m, n, ld, layer sizes, n_layers, X, y, n_rows, means, row_lppd,
+    # row_pwaic, ens_mean, ens_var, loglik, sample_loglik, summary, stream
+    lib.sgmcmc_score_abi_version.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_bnn_score_" + sfx)
+        f.argtypes = [ctypes.POINTER(_vp), _ci, _sz, _sz, ctypes.POINTER(_ci), _ci, _vp, _vp, _sz] + [_vp] * 8 + [_vp]
+        f.restype = _ci
 
 
 def lib():
@@ -267,6 +276,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: posterior-predictive add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_chains_abi_version() != CHAINS_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: many-chains diagnostics add-on (chains ABI) version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_score_abi_version() != SCORE_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: held-out-score add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

@@ -17,7 +17,7 @@ __all__ = [
     "moments_update", "rhat_pack", "rhat_finish", "summary",
     "LaunchConfig", "KernelEvents", "StepOpts", "step_stats_records", "step_scalars", "toy_chains", "set_launch_config", "get_launch_config", "summary_workspace", "counter_add", "StepStats", "bnn_head", "bnn_dense_tanh_backward", "bnn_dense_tanh_backward_fits", "colsum_finish", "tanh_backward", "tanh_backward_colsum", "bnn_last_layer_backward", "bnn_fused_sghmc_steps", "step_stats_finish",
     "bnn_fused_sgld_steps", "bnn_fused_rsghmc_steps", "bnn_fused_steps", "step_scalars_table", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
-    "ess_variogram", "bnn_predict", "bnn_predict_row_tile", "chain_diag",
+    "ess_variogram", "bnn_predict", "bnn_predict_row_tile", "chain_diag", "bnn_score",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -524,6 +524,52 @@ def bnn_predict_row_tile(layer_sizes, dtype=torch.float32):
     return tile
 
 
+def _bnn_trace_arguments(what, noun, chains, layer_sizes, X):
+    """The chain handling ``bnn_predict`` and ``bnn_score`` share: ``(f, mats, sizes, n, ld)`` -- the entry
+    ``sgmcmc_<what>_<dtype>``, the chain matrices that go into its pointer table (a 3-D tensor whose chains lie back to back
+    is ONE matrix), the layer sizes, the rows per matrix and their pitch -- after the checks of the chains and of ``X``."""
+    if torch.is_tensor(chains):
+        if chains.dim() == 2:
+            mats = [chains]
+        elif chains.dim() == 3:
+            m3, n3, P3 = (int(v) for v in chains.shape)
+            if m3 >= 1 and n3 >= 1 and (m3 == 1 or chains.stride(0) == n3 * chains.stride(1)):
+                # the chains lie back to back at one row pitch: one matrix of m * n rows, no pointer table
+                mats = [chains.as_strided((m3 * n3, P3), (chains.stride(1), chains.stride(2)), chains.storage_offset())]
+            else:
+                mats = list(chains.unbind(0))
+        else:
+            raise ValueError(what + ": chains must be (n, P), (m, n, P) or a sequence of (n, P) tensors")
+    else:
+        mats = list(chains)
+    if not mats:
+        raise ValueError(what + ": no chains")
+    first = mats[0]
+    for x in mats:
+        if not x.is_cuda:
+            raise SgmcmcLibraryError("pysgmcmc_amd: trace lives on %s; %s runs "
+                                     "only as a HIP kernel on an AMD GPU (no CPU fallback)." % (x.device, noun))
+        if x.dim() != 2 or x.shape != first.shape:
+            raise ValueError(what + ": every chain must be an (n, P) matrix of the same shape")
+        if x.dtype != first.dtype or x.device != first.device:
+            raise TypeError(what + ": the chains must share a dtype and a device")
+    f = getattr(lib(), "sgmcmc_" + what + "_" + _sfx(first))
+    sizes = [int(v) for v in layer_sizes]
+    n, P = int(first.shape[0]), int(first.shape[1])
+    if len(sizes) < 2 or P < _bnn_n_params(sizes):
+        raise ValueError(what + ": the traces are %d wide, layer sizes %s need %d parameters" % (
+            P, sizes, _bnn_n_params(sizes) if len(sizes) >= 2 else -1))
+    ld = int(first.stride(0)) if n > 1 else P
+    for x in mats:
+        if (P > 1 and x.stride(1) != 1) or (n > 1 and x.stride(0) != ld):
+            raise ValueError(what + ": rows must be dense and %d elements apart in every chain" % ld)
+    if not torch.is_tensor(X) or X.dtype != first.dtype or X.device != first.device:
+        raise TypeError(what + ": X must be a %s tensor on %s" % (first.dtype, first.device))
+    if X.dim() != 2 or int(X.shape[1]) != sizes[0] or not X.is_contiguous():
+        raise ValueError(what + ": X must be a contiguous (N, %d) matrix, got %s" % (sizes[0], tuple(X.shape)))
+    return f, mats, sizes, n, ld
+
+
 def bnn_predict(chains, layer_sizes, X, means, noise_var=None, ens_mean=None, ens_var=None):
     """K11 (``include/sgmcmc_hip_predict.h``): the outputs of ``S`` sampled networks of a small tanh-MLP BNN at the rows
     of ``X``, read from device traces, and their ensemble moments, in one call without host synchronisation.
@@ -536,45 +582,9 @@ def bnn_predict(chains, layer_sizes, X, means, noise_var=None, ens_mean=None, en
     dtype. ``means``: ``(S, N)`` of that dtype, required (also the reduction's only scratch). ``noise_var``: ``(S,)`` of
     that dtype or None. ``ens_mean``, ``ens_var``: float64 ``(N,)``, both or neither. Returns ``means``."""
     import ctypes
-    if torch.is_tensor(chains):
-        if chains.dim() == 2:
-            mats = [chains]
-        elif chains.dim() == 3:
-            m3, n3, P3 = (int(v) for v in chains.shape)
-            if m3 >= 1 and n3 >= 1 and (m3 == 1 or chains.stride(0) == n3 * chains.stride(1)):
-                # the chains lie back to back at one row pitch: one matrix of m * n rows, no pointer table
-                mats = [chains.as_strided((m3 * n3, P3), (chains.stride(1), chains.stride(2)), chains.storage_offset())]
-            else:
-                mats = list(chains.unbind(0))
-        else:
-            raise ValueError("bnn_predict: chains must be (n, P), (m, n, P) or a sequence of (n, P) tensors")
-    else:
-        mats = list(chains)
-    if not mats:
-        raise ValueError("bnn_predict: no chains")
+    f, mats, sizes, n, ld = _bnn_trace_arguments("bnn_predict", "the posterior predictive of device traces", chains,
+                                                 layer_sizes, X)
     first = mats[0]
-    for x in mats:
-        if not x.is_cuda:
-            raise SgmcmcLibraryError("pysgmcmc_amd: trace lives on %s; the posterior predictive of device traces runs "
-                                     "only as a HIP kernel on an AMD GPU (no CPU fallback)." % x.device)
-        if x.dim() != 2 or x.shape != first.shape:
-            raise ValueError("bnn_predict: every chain must be an (n, P) matrix of the same shape")
-        if x.dtype != first.dtype or x.device != first.device:
-            raise TypeError("bnn_predict: the chains must share a dtype and a device")
-    f = getattr(lib(), "sgmcmc_bnn_predict_" + _sfx(first))
-    sizes = [int(v) for v in layer_sizes]
-    n, P = int(first.shape[0]), int(first.shape[1])
-    if len(sizes) < 2 or P < _bnn_n_params(sizes):
-        raise ValueError("bnn_predict: the traces are %d wide, layer sizes %s need %d parameters" % (
-            P, sizes, _bnn_n_params(sizes) if len(sizes) >= 2 else -1))
-    ld = int(first.stride(0)) if n > 1 else P
-    for x in mats:
-        if (P > 1 and x.stride(1) != 1) or (n > 1 and x.stride(0) != ld):
-            raise ValueError("bnn_predict: rows must be dense and %d elements apart in every chain" % ld)
-    if not torch.is_tensor(X) or X.dtype != first.dtype or X.device != first.device:
-        raise TypeError("bnn_predict: X must be a %s tensor on %s" % (first.dtype, first.device))
-    if X.dim() != 2 or int(X.shape[1]) != sizes[0] or not X.is_contiguous():
-        raise ValueError("bnn_predict: X must be a contiguous (N, %d) matrix, got %s" % (sizes[0], tuple(X.shape)))
     S, N = len(mats) * n, int(X.shape[0])
     for out, dt, numel, name in ((means, first.dtype, S * N, "means"), (noise_var, first.dtype, S, "noise_var"),
                                  (ens_mean, torch.float64, N, "ens_mean"), (ens_var, torch.float64, N, "ens_var")):
@@ -594,6 +604,44 @@ def bnn_predict(chains, layer_sizes, X, means, noise_var=None, ens_mean=None, en
                _ptr(noise_var), _ptr(ens_mean), _ptr(ens_var), _stream(first))
     check(rc, "sgmcmc_bnn_predict")
     return means
+
+
+def bnn_score(chains, layer_sizes, X, y, means, row_lppd, row_pwaic, ens_mean, ens_var, loglik=None, sample_loglik=None,
+              summary=None):
+    """K13 (``include/sgmcmc_hip_score.h``): the held-out score of ``S`` sampled networks of a small tanh-MLP BNN at the
+    rows of ``X`` against the targets ``y``, read from device traces, in one call without host synchronisation.
+
+    ``chains``, ``layer_sizes``, ``X``: as for :func:`bnn_predict`. ``y``: ``(N,)`` of the chains' dtype, in the units the
+    networks work in. ``means``: ``(S, N)`` of that dtype, required: K11's output, the reductions' input. ``row_lppd``,
+    ``row_pwaic``, ``ens_mean``, ``ens_var``: float64 ``(N,)``, required: per row the log pointwise predictive density, the
+    sample variance over the networks of the pointwise log density, and K11's ensemble moments. Optional, float64:
+    ``loglik`` ``(S, N)``, the pointwise log densities; ``sample_loglik`` ``(S,)``, their sums over the rows; ``summary``
+    ``(3,)``: ``sum(row_lppd)``, ``sum(row_pwaic)``, ``sum((ens_mean - y)^2)``. Returns ``row_lppd``."""
+    import ctypes
+    f, mats, sizes, n, ld = _bnn_trace_arguments("bnn_score", "the held-out score of device traces", chains, layer_sizes, X)
+    first = mats[0]
+    S, N = len(mats) * n, int(X.shape[0])
+    f64 = torch.float64
+    for out, dt, numel, name, required in (
+            (y, first.dtype, N, "y", True), (means, first.dtype, S * N, "means", True), (row_lppd, f64, N, "row_lppd", True),
+            (row_pwaic, f64, N, "row_pwaic", True), (ens_mean, f64, N, "ens_mean", True), (ens_var, f64, N, "ens_var", True),
+            (loglik, f64, S * N, "loglik", False), (sample_loglik, f64, S, "sample_loglik", False),
+            (summary, f64, 3, "summary", False)):
+        if out is None:
+            if required:
+                raise ValueError("bnn_score: %s is required" % name)
+            continue
+        if not torch.is_tensor(out) or out.dtype != dt:
+            raise TypeError("bnn_score: %s must be a %s tensor" % (name, dt))
+        if out.numel() != numel or out.device != first.device:
+            raise ValueError("bnn_score: %s must hold %d elements on %s" % (name, numel, first.device))
+    table = (ctypes.c_void_p * len(mats))(*[x.data_ptr() for x in mats])
+    with torch.cuda.device(first.device):
+        rc = f(table, len(mats), n, ld, (ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, _ptr(X), _ptr(y), N, _ptr(means),
+               _ptr(row_lppd), _ptr(row_pwaic), _ptr(ens_mean), _ptr(ens_var), _ptr(loglik), _ptr(sample_loglik),
+               _ptr(summary), _stream(first))
+    check(rc, "sgmcmc_bnn_score")
+    return row_lppd
 
 
 def summary_workspace(device):

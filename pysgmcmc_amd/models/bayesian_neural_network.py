@@ -1093,3 +1093,50 @@ class BayesianNeuralNetwork(object):
             ensemble_mean = zero_mean_unit_var_unnormalization(ensemble_mean, self.y_mean, self.y_std)
             ensemble_var = ensemble_var * self.y_std ** 2
         return ensemble_mean, ensemble_var
+
+    def score(self, X_test, y_test, on_device=False):
+        """Held-out score of the kept networks at ``X_test (N, D)`` against ``y_test (N,)`` (extension; the reference's
+        ``diagnostics/model_diagnostics.py`` is a placeholder): a dict of host values ``lppd`` (the mean over the rows of
+        ``row_lppd``), ``p_waic``, ``elpd_waic = sum(row_lppd) - p_waic``, ``rmse`` of the ensemble mean, and the ``(N,)``
+        arrays ``row_lppd`` (log of the mean over the networks of each network's Gaussian density of ``y_test[r]``) and
+        ``row_pwaic`` (the sample variance over the networks of the log densities).
+
+        Inputs and targets are normalised as ``train`` normalised them and rounded to the model's dtype as ``train`` rounded
+        them; the results are in the caller's units: a density of ``y`` is the normalised one divided by ``y_std``, so
+        ``row_lppd`` is shifted by ``-log(y_std)``, ``rmse`` scaled by ``y_std`` and ``p_waic`` unchanged.
+
+        Default: ``_network_outputs`` and ``diagnostics.model_diagnostics`` (numpy float64 on the host).
+        ``on_device=True``: the kept-network matrix goes through K13 (``models.heldout_score``); a net the kernel refuses
+        raises the library's error (no fallback)."""
+        from pysgmcmc_amd.diagnostics import model_diagnostics
+        assert X_test.ndim == 2
+        if not self.is_trained:
+            raise ValueError("Calling `bnn.score()` on an untrained Bayesian Neural Network 'bnn' is not supported! "
+                             "Please call `bnn.train()` before calling `bnn.score()`")
+        y = np.asarray(y_test, dtype=np.float64).reshape(-1)
+        if y.shape[0] != X_test.shape[0]:
+            raise ValueError("bnn.score: X_test has %d rows, y_test %d" % (X_test.shape[0], y.shape[0]))
+        x = zero_mean_unit_var_normalization(X_test, self.x_mean, self.x_std)[0] if self.normalize_input else X_test
+        y_std = float(self.y_std) if self.normalize_output else 1.0
+        if self.normalize_output:
+            y = zero_mean_unit_var_normalization(y, self.y_mean, self.y_std)[0]
+        y = torch.as_tensor(np.ascontiguousarray(y), dtype=self._torch_dtype)           # train's rounding of the targets
+        if on_device:
+            from pysgmcmc_amd.models.scoring import heldout_score
+            flat, sizes = self._kept_networks_matrix()
+            xd = torch.as_tensor(np.ascontiguousarray(x), dtype=self._torch_dtype, device=flat.device)
+            got = heldout_score(flat, xd, y.to(flat.device), sizes)
+            row_lppd, row_pwaic = got.row_lppd.cpu().numpy(), got.row_pwaic.cpu().numpy()
+            p_waic, rmse = float(got.p_waic), float(got.rmse)
+            lppd_sum = float(got.elpd_waic) + p_waic
+        else:
+            outputs = self._network_outputs(x)                               # (nets, N, 2)
+            y64 = y.double().numpy()
+            loglik = model_diagnostics.pointwise_log_likelihood(outputs[:, :, 0], outputs[:, 0, 1], y64)
+            _, p_waic, _, row_lppd, row_pwaic = model_diagnostics.waic(loglik)
+            p_waic, lppd_sum = float(p_waic), float(row_lppd.sum())
+            rmse = model_diagnostics.ensemble_rmse(outputs[:, :, 0], y64)
+        n_rows, shift = row_lppd.shape[0], float(np.log(y_std))
+        lppd_sum -= n_rows * shift
+        return dict(lppd=lppd_sum / n_rows, p_waic=p_waic, elpd_waic=lppd_sum - p_waic, rmse=rmse * y_std,
+                    row_lppd=row_lppd - shift, row_pwaic=row_pwaic)

@@ -1,0 +1,55 @@
+"""Held-out score of a small tanh-MLP BNN from device-resident traces, in one device call.
+
+The reference leaves model diagnostics open (``pysgmcmc/diagnostics/model_diagnostics.py`` is a placeholder). Here the
+samples stay where ``FusedBNNChains.collect`` / ``DeviceTrace.record`` left them: ``heldout_score`` hands the trace and the
+held-out targets to K13 (``kernels.bnn_score``, ``include/sgmcmc_hip_score.h``), which runs K11's forward pass and reduces
+the pointwise Gaussian log densities over the samples and the rows in float64 on the device. Nothing here waits for the
+host. ``diagnostics.model_diagnostics`` states the same quantities in numpy on the host.
+"""
+import collections
+
+import torch
+
+from pysgmcmc_amd import kernels
+from pysgmcmc_amd.models.predictive import _trace_arguments
+
+__all__ = ["HeldOutScore", "heldout_score"]
+
+HeldOutScore = collections.namedtuple("HeldOutScore", ["lppd", "p_waic", "elpd_waic", "rmse", "row_lppd", "row_pwaic",
+                                                       "ens_mean", "ens_var", "sample_loglik", "loglik"])
+HeldOutScore.__doc__ = """What :func:`heldout_score` returns, all device tensors; the scalars are 0-d float64.
+
+``lppd``: the mean over the rows of ``row_lppd``. ``p_waic``: the sum of ``row_pwaic``. ``elpd_waic``: ``sum(row_lppd) -
+p_waic``. ``rmse``: of the ensemble mean against ``y``. ``row_lppd``, ``row_pwaic``, ``ens_mean``, ``ens_var``: float64
+``(N,)``. ``sample_loglik``: float64 ``(S,)`` or None. ``loglik``: float64 ``(S, N)`` or None."""
+
+
+def heldout_score(traces, X, y, layer_sizes, pointwise=False, per_sample=False):
+    """Score of the networks sampled in ``traces`` against the held-out targets ``y`` at the rows of ``X``.
+
+    ``traces``, ``X``, ``layer_sizes``: what :func:`~pysgmcmc_amd.models.posterior_predictive` accepts, refused alike. ``y``:
+    ``(N,)`` device tensor of the traces' dtype, in the units the networks work in (normalised like the training targets).
+    With ``S`` sampled networks, ``l[s][r]`` the Gaussian log density of ``y[r]`` under network ``s`` (mean: its output,
+    variance: ``exp(log_var_s) + 1e-16``):
+
+    * ``row_lppd[r] = log mean_s exp(l[s][r])``, evaluated with the row's maximum taken out; ``lppd`` is its mean over the rows
+    * ``row_pwaic[r]`` = the sample variance over ``s`` of ``l[s][r]`` (0 for one sample); ``p_waic`` is its sum
+    * ``elpd_waic = sum(row_lppd) - p_waic``; ``rmse = sqrt(mean((ens_mean - y)^2))``
+    * ``pointwise=True`` also returns ``loglik`` ``(S, N)``; ``per_sample=True`` ``sample_loglik[s] = sum_r l[s][r]``
+
+    Returns a :class:`HeldOutScore` of device tensors without host synchronisation. Allocates its outputs (and the ``(S, N)``
+    means the reductions read) and nothing else."""
+    chains, sizes, first, S, N = _trace_arguments("heldout_score", traces, X, layer_sizes, y)
+    if N == 0:
+        raise ValueError("heldout_score: X holds no rows, so there is nothing to score")
+    dev, f64 = first.device, torch.float64
+    means = torch.empty(S, N, dtype=first.dtype, device=dev)
+    row_lppd, row_pwaic, ens_mean, ens_var = (torch.empty(N, dtype=f64, device=dev) for _ in range(4))
+    loglik = torch.empty(S, N, dtype=f64, device=dev) if pointwise else None
+    sample_loglik = torch.empty(S, dtype=f64, device=dev) if per_sample else None
+    summary = torch.empty(3, dtype=f64, device=dev)
+    kernels.bnn_score(chains, sizes, X, y, means, row_lppd, row_pwaic, ens_mean, ens_var, loglik=loglik,
+                      sample_loglik=sample_loglik, summary=summary)
+    return HeldOutScore(lppd=summary[0] / N, p_waic=summary[1], elpd_waic=summary[0] - summary[1],
+                        rmse=torch.sqrt(summary[2] / N), row_lppd=row_lppd, row_pwaic=row_pwaic, ens_mean=ens_mean,
+                        ens_var=ens_var, sample_loglik=sample_loglik, loglik=loglik)

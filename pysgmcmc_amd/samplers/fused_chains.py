@@ -107,8 +107,8 @@ class FusedBNNChains(object):
     def collect(self, n_samples, every=100):
         """``n_samples`` thinned snapshots of all chains: a ``[n_chains, n_samples, n_params]`` device tensor, written
         by ONE launch of ``n_samples * every`` steps that keeps every ``every``-th theta itself (no launch boundary and no
-        copy per snapshot), ready for :meth:`diagnose` (R-hat and ESS of every parameter over ALL the chains) and
-        :meth:`predict`. ``diagnostics.device_trace.effective_n_all`` takes up to 64 of the chains (``t[:64]``);
+        copy per snapshot), ready for :meth:`diagnose` (R-hat and ESS of every parameter over ALL the chains),
+        :meth:`predict` and :meth:`score`. ``diagnostics.device_trace.effective_n_all`` takes up to 64 of the chains (``t[:64]``);
         ``diagnostics.sampler_diagnostics.gelman_rubin_from_chains`` works on a float64 copy, ``effective_n`` on one parameter."""
         n_samples, every = int(n_samples), int(every)
         a = self.samplers[0].arena
@@ -135,6 +135,20 @@ class FusedBNNChains(object):
         if not torch.is_tensor(X):
             X = torch.as_tensor(np.asarray(X), dtype=self.storage.dtype, device=self.storage.device)
         return posterior_predictive(trace, X, self.samplers[0]._bnn_layer_sizes(), **kw)
+
+    def score(self, X, y, trace, **kw):
+        """Held-out score of the samples in ``trace`` (what :meth:`collect` returns, or anything ``models.heldout_score``
+        accepts) against the targets ``y`` at the rows of ``X``, with the group's own layer sizes, in one device call:
+        ``chains.collect(n, every)`` -> ``chains.diagnose(t)`` -> ``chains.predict(X, t)`` -> ``chains.score(X, y, t)``
+        never copies a parameter or a prediction to the host. ``X``, ``y``: device tensors of the chains' dtype, or arrays
+        that are uploaded; normalised like the training data. Returns a ``models.HeldOutScore`` of device tensors (lppd,
+        WAIC, RMSE and their per-row parts; ``pointwise=True`` / ``per_sample=True`` add the log densities)."""
+        from pysgmcmc_amd.models.scoring import heldout_score
+        if not torch.is_tensor(X):
+            X = torch.as_tensor(np.asarray(X), dtype=self.storage.dtype, device=self.storage.device)
+        if not torch.is_tensor(y):
+            y = torch.as_tensor(np.asarray(y), dtype=self.storage.dtype, device=self.storage.device)
+        return heldout_score(trace, X, y, self.samplers[0]._bnn_layer_sizes(), **kw)
 
     @classmethod
     def for_dataset(cls, X, y, n_chains, hidden=(50, 50, 50), batch_size=20, seed=0, dtype=torch.float32,
