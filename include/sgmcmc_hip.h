@@ -60,7 +60,7 @@ typedef void *sgmcmc_stream_t;     /* hipStream_t */
  *     sgmcmc_rsghmc_step_f32 sgmcmc_rsghmc_step_f64
  *     sgmcmc_sghmc_scalars_f32 sgmcmc_sghmc_scalars_f64 sgmcmc_sgld_scalars_f32 sgmcmc_sgld_scalars_f64
  *     sgmcmc_rsghmc_scalars_f32 sgmcmc_rsghmc_scalars_f64 sgmcmc_counter_add_u64
- *     sgmcmc_step_stats_records sgmcmc_step_stats_workspace_bytes sgmcmc_step_stats_finish
+ *     sgmcmc_step_stats_records sgmcmc_step_stats_records_sized sgmcmc_step_stats_workspace_bytes sgmcmc_step_stats_finish
  *     sgmcmc_philox_normal_f32 sgmcmc_philox_normal_f64 sgmcmc_philox_bits_u32
  *     sgmcmc_moments_update_f32 sgmcmc_moments_update_f64
  *     sgmcmc_rhat_pack_f32 sgmcmc_rhat_pack_f64 sgmcmc_rhat_finish_f32 sgmcmc_rhat_finish_f64
@@ -127,9 +127,10 @@ int sgmcmc_event_synchronize(void *event);      /* host waits until the event ha
  *                under the remaining backward GEMMs -- gives exactly the chain the single launch gives.
  *   stats_record_base / stats_record_total: with a stats workspace, block b of this launch writes statistics record
  *                stats_record_base + b and the workspace header is set to stats_record_total records (0 = this launch's
- *                own): the slices of one step share one workspace. sgmcmc_step_stats_records() gives a launch's count.
+ *                own): the slices of one step share one workspace. sgmcmc_step_stats_records_sized() gives a launch's count.
  *   stats_select:   0 = every statistic the operator produces; SGMCMC_STATS_THETA_SQ = only sum theta'^2 (the one the
- *                BNN loss head consumes; the other three are written as 0 and cost no reduction work).
+ *                BNN loss head consumes; the other three are written as 0 and cost no reduction work), on every launch
+ *                variant: single pass, grid-capped, element-wise, injected or in-register noise.
  *   flags:       SGMCMC_STEP_HBM_RESIDENT: the launch is part of a working set larger than the Infinity Cache even if
  *                this slice alone is not (the auto geometry then picks what it picks for the whole arena).
  *                SGMCMC_STEP_SKIP_MINV_STORE (adapt = 1 only): do not write minv this step (44 instead of 48 B/param
@@ -177,9 +178,17 @@ typedef struct sgmcmc_step_opts {
     uint32_t reserved0;           /* 0 */
 } sgmcmc_step_opts_t;
 
-/* Number of statistics records (one per block = the grid) a vector-path step launch of n elements writes under
- * `launch` (block_threads must be explicit there: 64..256), or 0 on invalid arguments.                          */
+/* Number of statistics records (one per block = the grid) a vector-path step launch of n elements of elem_bytes bytes
+ * (4 = the f32 entry points, 8 = the f64 ones) writes under `launch` (block_threads must be explicit there: 64..256), or 0 on
+ * invalid arguments: min(max_blocks, max(1, ceil((n / 4) / (block_threads * q)))) with n / 4 rounded DOWN (the ragged tail
+ * rides on the last lane), q = quads_per_thread for f32 and q = 1 for f64 (an f64 launch streams one quad per lane whatever
+ * quads_per_thread says). The element-wise path (some array not 16-byte aligned) always runs one quad per lane and counts the
+ * ragged tail as a quad of its own: min(max_blocks, max(1, ceil(ceil(n / 4) / block_threads))) records, in both dtypes -- the
+ * same count unless n / 4 is a multiple of block_threads and n is no multiple of 4 (or q > 1). Either way the launch writes
+ * its own count into the workspace header when stats_record_total is 0.
+ * sgmcmc_step_stats_records(n, launch) = sgmcmc_step_stats_records_sized(n, 4, launch).                              */
 size_t sgmcmc_step_stats_records(size_t n, const sgmcmc_launch_t *launch);
+size_t sgmcmc_step_stats_records_sized(size_t n, size_t elem_bytes, const sgmcmc_launch_t *launch);
 
 /* K1 -- fused SGHMC step. Replaces the op chain pysgmcmc/samplers/sghmc.py:165-251
  * (+ constants :111-117) and the burn-in switch pysgmcmc/samplers/base_classes.py:432-456.

@@ -189,6 +189,8 @@ def _declare(lib):
     lib.sgmcmc_step_stats_workspace_bytes.restype = _sz
     lib.sgmcmc_step_stats_records.argtypes = [_sz, _lp]
     lib.sgmcmc_step_stats_records.restype = _sz
+    lib.sgmcmc_step_stats_records_sized.argtypes = [_sz, _sz, _lp]
+    lib.sgmcmc_step_stats_records_sized.restype = _sz
     lib.sgmcmc_step_stats_finish.argtypes = [_vp, _vp, _vp]
     lib.sgmcmc_step_stats_finish.restype = _ci
     # include/sgmcmc_hip_diag.h

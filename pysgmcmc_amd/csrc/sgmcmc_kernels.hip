@@ -307,14 +307,17 @@ int sgmcmc_device_count(void)
 
 // header + one record per block of the smallest block size (64 lanes)
 size_t sgmcmc_step_stats_workspace_bytes(size_t n) { return (max_grid_for(n) + 1) * 4 * sizeof(double); }
-size_t sgmcmc_step_stats_records(size_t n, const sgmcmc_launch_t *launch_in)
+size_t sgmcmc_step_stats_records_sized(size_t n, size_t elem_bytes, const sgmcmc_launch_t *launch_in)
 {
     LaunchCfg cfg;
     if (!launch_in || resolve_launch(launch_in, cfg) != 0) return 0;
     if (cfg.block_threads <= 0) { fail(SGMCMC_EINVAL, "step_stats_records: launch.block_threads must be explicit"); return 0; }
-    const size_t want = want_blocks(n, cfg.block_threads, cfg.qpt);
+    if (elem_bytes != 4 && elem_bytes != 8) { fail(SGMCMC_EINVAL, "step_stats_records: elem_bytes must be 4 (f32) or 8 (f64)"); return 0; }
+    // launch(): f64 operators stream one quad per lane whatever quads_per_thread asks for
+    const size_t want = want_blocks(n, cfg.block_threads, elem_bytes == 8 ? 1 : cfg.qpt);
     return want < (size_t)cfg.max_blocks ? want : (size_t)cfg.max_blocks;
 }
+size_t sgmcmc_step_stats_records(size_t n, const sgmcmc_launch_t *launch_in) { return sgmcmc_step_stats_records_sized(n, 4, launch_in); }
 int sgmcmc_step_stats_finish(const void *stats_ws, double *stats_out, sgmcmc_stream_t stream)
 {
     if (!stats_ws || !stats_out) return fail(SGMCMC_EINVAL, "step_stats_finish: NULL argument");

@@ -217,8 +217,8 @@ __global__ void __launch_bounds__(256) stream_quads_vec(const Op op_in, size_t n
         stats_block_write<T, tsq_only ? (Op::stats_mask & 1u) : Op::stats_mask>(acc, op.stats_part, ex.part_base, ex.part_total, block, blocks);
 }
 
-// element-wise path for misaligned arrays: same quads, same results
-template <typename Op, bool STATS>
+// element-wise path for misaligned arrays: same quads, same results (STATS as in stream_quads_vec)
+template <typename Op, int STATS>
 __global__ void __launch_bounds__(256) stream_quads_scalar(const Op op_in, size_t n, const StreamExtras<typename Op::real> ex)
 {
     Op op = op_in;
@@ -226,7 +226,8 @@ __global__ void __launch_bounds__(256) stream_quads_scalar(const Op op_in, size_
     const size_t G = (size_t)gridDim.x * blockDim.x;
     const size_t nq = (n + 3) / 4;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    constexpr bool stats = STATS;
+    constexpr bool stats = STATS != 0;
+    constexpr bool tsq_only = STATS == 2;
     for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += G) {
         size_t left = n - 4 * q;
         int cnt = left >= 4 ? 4 : (int)left;
@@ -234,10 +235,11 @@ __global__ void __launch_bounds__(256) stream_quads_scalar(const Op op_in, size_
         op.load_part_(q, cnt, R);
         op.compute(q, R);
         op.store_part_(q, cnt, R);
-        if constexpr (stats) op.template accumulate<false>(R, cnt, acc);
+        if constexpr (stats) op.template accumulate<tsq_only>(R, cnt, acc);
     }
     if constexpr (stats)
-        stats_block_write<typename Op::real, Op::stats_mask>(acc, op.stats_part, ex.part_base, ex.part_total, blockIdx.x, gridDim.x);
+        stats_block_write<typename Op::real, tsq_only ? (Op::stats_mask & 1u) : Op::stats_mask>(acc, op.stats_part, ex.part_base, ex.part_total,
+                                                                                                blockIdx.x, gridDim.x);
 }
 
 // --------------------------------------------------------------------------
@@ -360,9 +362,11 @@ int launch_vec(const Op &op, size_t n, const LaunchCfg &cfg, const StepExtras<ty
     StreamExtras<typename Op::real> ex = se.ex;
     ex.copy_blocks = 0;
     if (moments_done) *moments_done = false;
+    // 0 = no statistics, 1 = all of the operator's, 2 = sum theta'^2 only (operators without statistics never see 2)
+    const int smode = with_stats ? se.stats_mode : 0;
+    constexpr bool has_stats = Op::stats_mask != 0u;
     if constexpr (QPT == 1) {
         if (want <= cap) {                                 // one quad per lane, whole array in one pass
-            const int smode = with_stats ? (FAST_VARIANTS ? se.stats_mode : 1) : 0;
             const bool mom = FAST_VARIANTS && se.want_moments;
             if (se.want_copy && se.copy_done != nullptr) { // the window gather rides in this launch: extra workgroups in front
                 ex.copy_blocks = side_copy_blocks(ex.cp, bt);
@@ -378,17 +382,20 @@ int launch_vec(const Op &op, size_t n, const LaunchCfg &cfg, const StepExtras<ty
                     if (smode == 2) SGMCMC_FAST(2, false); else if (smode == 1) SGMCMC_FAST(1, false); else SGMCMC_FAST(0, false);
                 }
             } else {
-                if (smode) SGMCMC_FAST(1, false); else SGMCMC_FAST(0, false);
+                if (smode == 2) { if constexpr (has_stats) SGMCMC_FAST(2, false); }
+                else if (smode == 1) SGMCMC_FAST(1, false);
+                else SGMCMC_FAST(0, false);
             }
 #undef SGMCMC_FAST
             hipError_t e1 = hipGetLastError();
             return e1 == hipSuccess ? 0 : hip_fail(e1, "launch stream_quads_vec");
         }
     }
-    if (with_stats)
-        SGMCMC_LAUNCH((stream_quads_vec<Op, QPT, NT, 1, true, false>), grid, bt, st, cfg, op, nq_full, tail, ex);
-    else
-        SGMCMC_LAUNCH((stream_quads_vec<Op, QPT, NT, 0, true, false>), grid, bt, st, cfg, op, nq_full, tail, ex);
+#define SGMCMC_LOOP(SM) SGMCMC_LAUNCH((stream_quads_vec<Op, QPT, NT, SM, true, false>), grid, bt, st, cfg, op, nq_full, tail, ex)
+    if (smode == 2) { if constexpr (has_stats) SGMCMC_LOOP(2); }
+    else if (smode == 1) SGMCMC_LOOP(1);
+    else SGMCMC_LOOP(0);
+#undef SGMCMC_LOOP
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_fail(e, "launch stream_quads_vec");
 }
@@ -401,17 +408,17 @@ int launch_scalar(const Op &op, size_t n, const LaunchCfg &cfg, const StepExtras
     if (want == 0) want = 1;
     size_t cap = (size_t)cfg.max_blocks;
     unsigned grid = (unsigned)(want < cap ? want : cap);
-    if (op.stats_part != nullptr)
-        SGMCMC_LAUNCH((stream_quads_scalar<Op, true>), grid, bt, st, cfg, op, n, se.ex);
-    else
-        SGMCMC_LAUNCH((stream_quads_scalar<Op, false>), grid, bt, st, cfg, op, n, se.ex);
+    const int smode = op.stats_part != nullptr ? se.stats_mode : 0;
+    if (smode == 2) { if constexpr (Op::stats_mask != 0u) SGMCMC_LAUNCH((stream_quads_scalar<Op, 2>), grid, bt, st, cfg, op, n, se.ex); }
+    else if (smode == 1) SGMCMC_LAUNCH((stream_quads_scalar<Op, 1>), grid, bt, st, cfg, op, n, se.ex);
+    else SGMCMC_LAUNCH((stream_quads_scalar<Op, 0>), grid, bt, st, cfg, op, n, se.ex);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_fail(e, "launch stream_quads_scalar");
 }
 
 // f32 ops honour the (quads_per_thread, nontemporal) knobs; f64 ops (a quad is already 32 B per lane per array) use one
-// quad per lane. FAST_VARIANTS: instantiate the sum-theta'^2-only and fused-moments forms of the single-pass kernel (the
-// in-register-noise step operators; injected-noise and utility operators keep the two basic forms).
+// quad per lane. FAST_VARIANTS: instantiate the fused-moments forms of the single-pass kernel (the in-register-noise step
+// operators). The sum-theta'^2-only reduction (sgmcmc_step_opts_t.stats_select) exists on every path of every step operator.
 template <typename Op, bool FAST_VARIANTS = false>
 int launch(const Op &op, size_t n, bool vec_ok, size_t bytes_per_elem, const sgmcmc_launch_t *launch_in,
            const StepExtras<typename Op::real> &se, bool *moments_done, hipStream_t st)

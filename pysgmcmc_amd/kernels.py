@@ -253,11 +253,14 @@ def _opts(opts, like):
     return ctypes.byref(opts._c)
 
 
-def step_stats_records(n, launch):
-    """Number of blocks (= statistics records) a vector-path step launch of ``n`` elements uses under ``launch``
-    (a :class:`LaunchConfig` with an explicit ``block_threads``)."""
+def step_stats_records(n, launch, dtype=torch.float32):
+    """Number of blocks (= statistics records) a vector-path step launch of ``n`` elements of ``dtype`` uses under ``launch``
+    (a :class:`LaunchConfig` with an explicit ``block_threads``). A float64 launch streams one quad per lane whatever
+    ``quads_per_thread`` says, so its count differs from the float32 one there."""
     import ctypes
-    blocks = int(lib().sgmcmc_step_stats_records(int(n), ctypes.byref(launch._c)))
+    if dtype not in _SFX:
+        raise TypeError("pysgmcmc_amd kernels support float32/float64, got %s" % dtype)
+    blocks = int(lib().sgmcmc_step_stats_records_sized(int(n), 4 if dtype == torch.float32 else 8, ctypes.byref(launch._c)))
     if blocks == 0:
         check(-1, "sgmcmc_step_stats_records")
     return blocks

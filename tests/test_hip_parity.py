@@ -195,7 +195,8 @@ def test_philox_normal_f64_tolerance(gpu, oracle):
 @pytest.mark.parametrize("npdt,thdt", DTYPES)
 def test_register_noise_equals_injected_stream(gpu, oracle, npdt, thdt):
     """xi == NULL path: the in-register Philox draw equals feeding the K5 stream as xi (bit-exact),
-    for the vector path, the ragged tail and every launch geometry."""
+    for the vector path, the ragged tail and four launch geometries of the SGHMC step. Every launch variant of every
+    operator (and of K5 itself) against the oracle: tests/test_step_launch_variants_gpu.py."""
     from pysgmcmc_amd import kernels
     n = 70003
     rng = np.random.default_rng(11)
