@@ -51,11 +51,13 @@ FUSED_TRACE_ABI_VERSION = 1   # SGMCMC_FUSED_TRACE_ABI_VERSION of include/sgmcmc
 PREDICT_ABI_VERSION = 1       # SGMCMC_PREDICT_ABI_VERSION of include/sgmcmc_hip_predict.h (the posterior-predictive add-on)
 CHAINS_ABI_VERSION = 1        # SGMCMC_CHAINS_ABI_VERSION of include/sgmcmc_hip_chains.h (the many-chains diagnostics add-on)
 SCORE_ABI_VERSION = 1         # SGMCMC_SCORE_ABI_VERSION of include/sgmcmc_hip_score.h (the held-out-score add-on)
+PREDICT_GRAD_ABI_VERSION = 1  # SGMCMC_PREDICT_GRAD_ABI_VERSION of include/sgmcmc_hip_predict_grad.h (the predictive-gradient add-on)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
 CHAINS_MAX_CHAINS = 4096
 SCORE_MAX_CHAINS = 64
+PREDICT_GRAD_MAX_CHAINS = 64
 
 _u64 = ctypes.c_uint64
 _sz = ctypes.c_size_t
@@ -250,6 +252,15 @@ def _declare(lib):
         f = getattr(lib, "sgmcmc_bnn_score_" + sfx)
         f.argtypes = [ctypes.POINTER(_vp), _ci, _sz, _sz, ctypes.POINTER(_ci), _ci, _vp, _vp, _sz] + [_vp] * 8 + [_vp]
         f.restype = _ci
+    # include/sgmcmc_hip_predict_grad.h: host array of chain matrices, m, n, ld, layer sizes, n_layers, X, n_rows, means, grads,
+    # ens_mean, ens_var, dmean, dvar, stream
+    lib.sgmcmc_predict_grad_abi_version.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_bnn_predict_grad_" + sfx)
+        f.argtypes = [ctypes.POINTER(_vp), _ci, _sz, _sz, ctypes.POINTER(_ci), _ci, _vp, _sz] + [_vp] * 6 + [_vp]
+        f.restype = _ci
+    lib.sgmcmc_bnn_predict_grad_row_tile.argtypes = [ctypes.POINTER(_ci), _ci, _sz]
+    lib.sgmcmc_bnn_predict_grad_row_tile.restype = _ci
 
 
 def lib():
@@ -280,6 +291,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: many-chains diagnostics add-on (chains ABI) version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_score_abi_version() != SCORE_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: held-out-score add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_predict_grad_abi_version() != PREDICT_GRAD_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: predictive-gradient add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

@@ -18,6 +18,7 @@ __all__ = [
     "LaunchConfig", "KernelEvents", "StepOpts", "step_stats_records", "step_scalars", "toy_chains", "set_launch_config", "get_launch_config", "summary_workspace", "counter_add", "StepStats", "bnn_head", "bnn_dense_tanh_backward", "bnn_dense_tanh_backward_fits", "colsum_finish", "tanh_backward", "tanh_backward_colsum", "bnn_last_layer_backward", "bnn_fused_sghmc_steps", "step_stats_finish",
     "bnn_fused_sgld_steps", "bnn_fused_rsghmc_steps", "bnn_fused_steps", "step_scalars_table", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
     "ess_variogram", "bnn_predict", "bnn_predict_row_tile", "chain_diag", "bnn_score",
+    "bnn_predict_grad", "bnn_predict_grad_row_tile",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -645,6 +646,57 @@ def bnn_score(chains, layer_sizes, X, y, means, row_lppd, row_pwaic, ens_mean, e
                _ptr(summary), _stream(first))
     check(rc, "sgmcmc_bnn_score")
     return row_lppd
+
+
+def bnn_predict_grad_row_tile(sizes, dtype=torch.float32):
+    """Test rows per tile of ``bnn_predict_grad``'s forward + backward launch for this net and dtype
+    (``sgmcmc_bnn_predict_grad_row_tile``: host arithmetic, nothing launched). Performance only; the results do not depend
+    on it."""
+    import ctypes
+    sizes = [int(v) for v in sizes]
+    esize = {torch.float32: 4, torch.float64: 8}[dtype]
+    tile = lib().sgmcmc_bnn_predict_grad_row_tile((ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, esize)
+    if tile < 1:
+        check(tile, "sgmcmc_bnn_predict_grad_row_tile")
+    return tile
+
+
+def bnn_predict_grad(chains, layer_sizes, X, means, grads, ens_mean=None, ens_var=None, dmean=None, dvar=None):
+    """K14 (``include/sgmcmc_hip_predict_grad.h``): the outputs of ``S`` sampled networks of a small tanh-MLP BNN at the
+    rows of ``X`` AND their gradients with respect to those rows, read from device traces, with the input gradients of the
+    ensemble mean and variance, in one call without host synchronisation.
+
+    ``chains``, ``layer_sizes``, ``X``: as for :func:`bnn_predict`; ``D0 = layer_sizes[0]``. ``means``: ``(S, N)`` of the
+    chains' dtype, required: K11's bits. ``grads``: ``(S, N, D0)`` of that dtype, required: ``grads[s, r, d]`` is the
+    derivative of ``means[s, r]`` with respect to ``X[r, d]``. ``ens_mean``, ``ens_var``: float64 ``(N,)``; ``dmean``,
+    ``dvar``: float64 ``(N, D0)``, the derivatives of ``ens_mean[r]`` and ``ens_var[r]`` with respect to ``X[r, d]``: all
+    four or none. Returns ``grads``."""
+    import ctypes
+    f, mats, sizes, n, ld = _bnn_trace_arguments("bnn_predict_grad", "the predictive gradients of device traces", chains,
+                                                 layer_sizes, X)
+    first = mats[0]
+    S, N, D0 = len(mats) * n, int(X.shape[0]), sizes[0]
+    f64 = torch.float64
+    for out, dt, numel, name, required in (
+            (means, first.dtype, S * N, "means", True), (grads, first.dtype, S * N * D0, "grads", True),
+            (ens_mean, f64, N, "ens_mean", False), (ens_var, f64, N, "ens_var", False),
+            (dmean, f64, N * D0, "dmean", False), (dvar, f64, N * D0, "dvar", False)):
+        if out is None:
+            if required:
+                raise ValueError("bnn_predict_grad: %s is required" % name)
+            continue
+        if not torch.is_tensor(out) or out.dtype != dt:
+            raise TypeError("bnn_predict_grad: %s must be a %s tensor" % (name, dt))
+        if out.numel() != numel or out.device != first.device:
+            raise ValueError("bnn_predict_grad: %s must hold %d elements on %s" % (name, numel, first.device))
+    if len({out is None for out in (ens_mean, ens_var, dmean, dvar)}) != 1:
+        raise ValueError("bnn_predict_grad: ens_mean, ens_var, dmean and dvar go together")
+    table = (ctypes.c_void_p * len(mats))(*[x.data_ptr() for x in mats])
+    with torch.cuda.device(first.device):
+        rc = f(table, len(mats), n, ld, (ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, _ptr(X), N, _ptr(means),
+               _ptr(grads), _ptr(ens_mean), _ptr(ens_var), _ptr(dmean), _ptr(dvar), _stream(first))
+    check(rc, "sgmcmc_bnn_predict_grad")
+    return grads
 
 
 def summary_workspace(device):

@@ -3,14 +3,23 @@
 The reference's ``predict`` (``pysgmcmc/models/bayesian_neural_network.py:560-630``) evaluates the kept networks one by one
 and reduces on the host. Here the samples stay where ``FusedBNNChains.collect`` / ``DeviceTrace.record`` left them:
 ``posterior_predictive`` hands the trace to K11 (``kernels.bnn_predict``, ``include/sgmcmc_hip_predict.h``), which runs every
-sampled network at every test row out of the LDS and reduces over the samples on the device. Nothing here waits for the host.
+sampled network at every test row out of the LDS and reduces over the samples on the device. ``predictive_gradients`` hands
+it to K14 (``kernels.bnn_predict_grad``, ``include/sgmcmc_hip_predict_grad.h``), which adds the backward sweep to the inputs:
+the gradients of the predictive mean and variance that an acquisition function is climbed with. Nothing here waits for the host.
 """
+import collections
+
 import torch
 
 from pysgmcmc_amd import kernels
 from pysgmcmc_amd.diagnostics.device_trace import _chain_matrices
 
-__all__ = ["posterior_predictive"]
+__all__ = ["posterior_predictive", "predictive_gradients", "PredictiveGradients"]
+
+PredictiveGradients = collections.namedtuple("PredictiveGradients", "mean var dmean dvar")
+PredictiveGradients.__doc__ = """What :func:`predictive_gradients` returns, float64 device tensors: ``mean`` and ``var``
+``(N,)``, the ensemble moments of :func:`posterior_predictive`; ``dmean`` and ``dvar`` ``(N, D0)``, their derivatives with
+respect to the inputs, ``dmean[r, d] = d mean[r] / d X[r, d]``."""
 
 
 def _trace_arguments(what, traces, X, layer_sizes, *targets):
@@ -81,3 +90,39 @@ def posterior_predictive(traces, X, layer_sizes, return_individual_predictions=F
     ens_var = torch.empty(N, dtype=torch.float64, device=dev)
     kernels.bnn_predict(chains, sizes, X, means, ens_mean=ens_mean, ens_var=ens_var)
     return ens_mean, ens_var
+
+
+def predictive_gradients(traces, X, layer_sizes, return_individual=False, scratch_bytes=1 << 30):
+    """Predictive moments at the rows of ``X`` of the networks sampled in ``traces`` AND their gradients with respect to
+    those rows: what a Bayesian-optimisation loop needs to climb an acquisition function (K14, ``kernels.bnn_predict_grad``,
+    ``include/sgmcmc_hip_predict_grad.h``).
+
+    ``traces``, ``X``, ``layer_sizes``: what :func:`posterior_predictive` accepts, refused alike; ``D0 = layer_sizes[0]``.
+
+    Returns device tensors, ``S`` = the number of samples: by default :class:`PredictiveGradients` ``(mean, var, dmean,
+    dvar)``, float64, ``(N,), (N,), (N, D0), (N, D0)``: the mean over the samples of the networks' outputs, their population
+    variance, and the derivatives of both with respect to ``X[r, d]``; with ``return_individual`` ``(means, grads)`` of the
+    traces' dtype, ``(S, N)`` and ``(S, N, D0)``: every network's output at every row and its input gradient.
+
+    The per-network gradients are ``S * N * D0`` elements. The default path therefore walks ``X`` in chunks of rows that keep
+    the ``means`` and ``grads`` of one chunk within ``scratch_bytes`` (at least one row per chunk) and reuses that scratch
+    from chunk to chunk on the stream; rows are independent, so the result has the same bits whatever the chunking. Nothing
+    here waits for the host."""
+    chains, sizes, first, S, N = _trace_arguments("predictive_gradients", traces, X, layer_sizes)
+    dev, dt, D0 = first.device, first.dtype, sizes[0]
+    if return_individual:
+        means = torch.empty(S, N, dtype=dt, device=dev)
+        grads = torch.empty(S, N, D0, dtype=dt, device=dev)
+        kernels.bnn_predict_grad(chains, sizes, X, means, grads)
+        return means, grads
+    f64 = torch.float64
+    out = PredictiveGradients(torch.empty(N, dtype=f64, device=dev), torch.empty(N, dtype=f64, device=dev),
+                              torch.empty(N, D0, dtype=f64, device=dev), torch.empty(N, D0, dtype=f64, device=dev))
+    per_row = S * (1 + D0) * first.element_size()
+    rows = max(1, min(N, int(scratch_bytes) // per_row))
+    scratch = torch.empty(S * rows * (1 + D0), dtype=dt, device=dev)
+    for lo in range(0, N, rows):
+        k = min(rows, N - lo)
+        kernels.bnn_predict_grad(chains, sizes, X[lo:lo + k], scratch[:S * k], scratch[S * rows:S * rows + S * k * D0],
+                                 *(t[lo:lo + k] for t in out))
+    return out

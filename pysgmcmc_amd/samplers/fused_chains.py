@@ -150,6 +150,17 @@ class FusedBNNChains(object):
             y = torch.as_tensor(np.asarray(y), dtype=self.storage.dtype, device=self.storage.device)
         return heldout_score(trace, X, y, self.samplers[0]._bnn_layer_sizes(), **kw)
 
+    def predictive_gradients(self, X, trace, **kw):
+        """Predictive moments of the samples in ``trace`` (what :meth:`collect` returns, or anything
+        ``models.predictive_gradients`` accepts) at the rows of ``X`` and their gradients with respect to those rows, with
+        the group's own layer sizes, on the device: what an acquisition function is climbed with. ``X``: a device tensor of
+        the chains' dtype, or an array that is uploaded; already normalised. Returns a ``models.PredictiveGradients`` of
+        float64 device tensors ``(mean, var, dmean, dvar)``, or ``(means, grads)`` with ``return_individual=True``."""
+        from pysgmcmc_amd.models.predictive import predictive_gradients
+        if not torch.is_tensor(X):
+            X = torch.as_tensor(np.asarray(X), dtype=self.storage.dtype, device=self.storage.device)
+        return predictive_gradients(trace, X, self.samplers[0]._bnn_layer_sizes(), **kw)
+
     @classmethod
     def for_dataset(cls, X, y, n_chains, hidden=(50, 50, 50), batch_size=20, seed=0, dtype=torch.float32,
                     device="cuda:0", stepsize=0.01, burn_in_steps=1000, mdecay=0.05, init_seed=None):
