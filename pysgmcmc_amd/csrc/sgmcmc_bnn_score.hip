@@ -3,8 +3,9 @@
 // the section 8(b) boundary). The reference leaves model diagnostics open (pysgmcmc/diagnostics/model_diagnostics.py); the
 // density is the one its BNN trains on (pysgmcmc/models/bayesian_neural_network.py:368).
 //
-// The forward pass is K11's: the entry calls sgmcmc_bnn_predict_* with no optional output, so `means` has K11's bits and a
-// net K11 refuses is refused with its text. Behind it on the same stream, every reduction in f64 in the header's order:
+// The forward pass is K11's: the entry calls sgmcmc_bnn_predict_* with no optional output, so `means` has K11's bits. A net
+// K11 refuses is refused with its text, by the rules both share (sgmcmc_bnn_small_net.hpp), under K11's name. Behind the
+// forward launch on the same stream, every reduction in f64 in the header's order:
 //   row kernel     lane = test row, 64-lane workgroups, so every access to means / loglik is a coalesced row segment. The
 //                  per-sample constants a_s, b_s go through the LDS in blocks of 64 samples (lane j forms those of sample
 //                  s0 + j), which puts barriers inside the sample loop: lanes behind n_rows stay in the loop and only skip
@@ -13,41 +14,21 @@
 //   sample kernel  one 256-lane workgroup per sample: lane j adds rows j, j + 256, ... ascending, then a fixed pairwise tree.
 //   summary kernel one 256-lane workgroup, the same order, three sums.
 // No atomics anywhere: equal inputs give equal bits whatever the launch.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-
-#include "sgmcmc_hip_predict.h"
-#include "sgmcmc_hip_score.h"
-
-#pragma clang fp contract(off)
-
-#include "sgmcmc_host.hpp"
-
-using namespace sgmcmc_host;
+#include "sgmcmc_bnn_small_net.hpp"
 
 namespace {
 
-constexpr int SCORE_MAX_LAYERS = 8;                        // K11's
-constexpr size_t SCORE_LDS_MAX = (size_t)160 * 1024;       // K11's: a net whose parameters need more is refused there
 constexpr int SCORE_ROW_THREADS = 64;                      // one wave: rows per workgroup AND samples per LDS block
 constexpr int SCORE_ROW_AHEAD = 16;                        // loads of means a lane keeps in flight
 constexpr int SCORE_SUM_THREADS = 256;
 constexpr double SCORE_LOG_2PI = 1.8378770664093453;
 
-template <typename T>
-struct ScoreChains {
-    const T *p[SGMCMC_SCORE_MAX_CHAINS];                   // by value in the kernel arguments: no device-side pointer table
-};
-
 // a_s and b_s of sample s (the header's statements)
 template <typename T>
-__device__ __forceinline__ void score_constants(const ScoreChains<T> &ch, size_t n, size_t ld, int n_params, size_t s,
+__device__ __forceinline__ void score_constants(const SmallNetChains<T> &ch, size_t n, size_t ld, int n_params, size_t s,
                                                 double &a, double &b)
 {
-    const size_t c = s / n;
-    const double lv = (double)ch.p[c][(s - c * n) * ld + (size_t)(n_params - 1)];
+    const double lv = (double)ch.row(s, n, ld)[n_params - 1];
     a = -0.5 * (SCORE_LOG_2PI + lv);
     b = 0.5 / (exp(lv) + 1e-16);
 }
@@ -80,7 +61,7 @@ __device__ __forceinline__ void score_tree(double *part, int tid)
 }
 
 template <typename T>
-__global__ void __launch_bounds__(SCORE_ROW_THREADS) bnn_score_row_kernel(const ScoreChains<T> ch, size_t n, size_t ld,
+__global__ void __launch_bounds__(SCORE_ROW_THREADS) bnn_score_row_kernel(const SmallNetChains<T> ch, size_t n, size_t ld,
                                                                           int n_params, size_t S, const T *__restrict__ means,
                                                                           const T *__restrict__ y, size_t n_rows,
                                                                           double *__restrict__ row_lppd,
@@ -159,7 +140,7 @@ __global__ void __launch_bounds__(SCORE_ROW_THREADS) bnn_score_row_kernel(const 
 
 // sample_loglik[s] = sum_r l[s][r]
 template <typename T>
-__global__ void __launch_bounds__(SCORE_SUM_THREADS) bnn_score_sample_kernel(const ScoreChains<T> ch, size_t n, size_t ld,
+__global__ void __launch_bounds__(SCORE_SUM_THREADS) bnn_score_sample_kernel(const SmallNetChains<T> ch, size_t n, size_t ld,
                                                                             int n_params, const T *__restrict__ means,
                                                                             const T *__restrict__ y, size_t n_rows,
                                                                             double *__restrict__ sample_loglik)
@@ -197,34 +178,8 @@ __global__ void __launch_bounds__(SCORE_SUM_THREADS) bnn_score_summary_kernel(co
         sq += e * e;
     }
     part[0][tid] = lppd; part[1][tid] = pwaic; part[2][tid] = sq;
-    __syncthreads();
-    for (int h = SCORE_SUM_THREADS / 2; h >= 1; h /= 2) {
-        if (tid < h) {
-            part[0][tid] += part[0][tid + h];
-            part[1][tid] += part[1][tid + h];
-            part[2][tid] += part[2][tid + h];
-        }
-        __syncthreads();
-    }
+    for (int k = 0; k < 3; ++k) score_tree(part[k], tid);
     if (tid < 3) summary[tid] = part[tid][0];
-}
-
-// n_params of a net K11's plan can take, 0 for one it refuses on its sizes alone (sgmcmc_bnn_predict.hip: predict_plan)
-size_t score_n_params(const int *layer_sizes, int n_layers, size_t esize)
-{
-    if (n_layers < 1 || n_layers > SCORE_MAX_LAYERS) return 0;
-    for (int l = 0; l <= n_layers; ++l)
-        if (layer_sizes[l] < 1) return 0;
-    if (layer_sizes[n_layers] != 1) return 0;
-    const size_t cap = SCORE_LDS_MAX / esize;              // no sum below grows past it: nothing wraps
-    size_t off = 0;
-    for (int l = 1; l <= n_layers; ++l) {
-        off += (size_t)layer_sizes[l - 1] * (size_t)layer_sizes[l];
-        if (off > cap) return 0;
-        off += (size_t)layer_sizes[l];
-        if (off + 1 > cap) return 0;
-    }
-    return off + 1;
 }
 
 inline int score_forward(const float *const *chains, int m, size_t n, size_t ld, const int *layer_sizes, int n_layers,
@@ -252,17 +207,13 @@ int bnn_score(const T *const *chains, int m, size_t n, size_t ld, const int *lay
         {row_pwaic, "row_pwaic"}, {ens_mean, "ens_mean"}, {ens_var, "ens_var"}};
     for (const auto &arg : required)
         if (!arg.p) return fail(SGMCMC_EINVAL, "%s: %s is NULL", what, arg.name);
-    ScoreChains<T> ch;
-    for (int c = 0; c < SGMCMC_SCORE_MAX_CHAINS; ++c) {
-        ch.p[c] = c < m ? chains[c] : nullptr;
-        if (c < m && !ch.p[c]) return fail(SGMCMC_EINVAL, "%s: chains[%d] is NULL", what, c);
-    }
-    const size_t n_params = score_n_params(layer_sizes, n_layers, sizeof(T));
-    if (n_params == 0) {
-        // a net K11 refuses on its sizes: its own text, from its own checks (it launches nothing before them)
-        const int rc = score_forward(chains, m, n, ld, layer_sizes, n_layers, X, n_rows, means, st);
-        return rc ? rc : fail(SGMCMC_EINVAL, "%s: the layer sizes are not a net the forward pass takes", what);
-    }
+    SmallNetChains<T> ch;
+    if (int rc = small_net_chains(what, chains, m, ch)) return rc;
+    // a net K11 refuses on its sizes or on its parameters alone: the shared rules under K11's name, so K11's text
+    SmallNet net{};
+    size_t n_params = 0;
+    if (int rc = small_net_rules("bnn_predict", layer_sizes, n_layers, net, n_params)) return rc;
+    if (int rc = small_net_offsets("bnn_predict", n_params, sizeof(T), net)) return rc;
     if (ld < n_params) return fail(SGMCMC_EINVAL, "%s: ld = %zu is smaller than n_params = %zu", what, ld, n_params);
     if (n > (size_t)INT32_MAX / (size_t)m)
         return fail(SGMCMC_EINVAL, "%s: m * n = %d * %zu samples, must be < 2^31", what, m, n);

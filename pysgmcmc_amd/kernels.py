@@ -516,16 +516,20 @@ def _bnn_n_params(sizes):
     return sum(sizes[l] * sizes[l + 1] + sizes[l + 1] for l in range(len(sizes) - 1)) + 1
 
 
-def bnn_predict_row_tile(layer_sizes, dtype=torch.float32):
-    """Test rows per tile of ``bnn_predict``'s forward launch for this net and dtype (``sgmcmc_bnn_predict_row_tile``:
-    host arithmetic, nothing launched). Performance only; the results do not depend on it."""
+def _bnn_row_tile(entry, layer_sizes, dtype):
     import ctypes
     sizes = [int(v) for v in layer_sizes]
     esize = {torch.float32: 4, torch.float64: 8}[dtype]
-    tile = lib().sgmcmc_bnn_predict_row_tile((ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, esize)
+    tile = getattr(lib(), entry)((ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, esize)
     if tile < 1:
-        check(tile, "sgmcmc_bnn_predict_row_tile")
+        check(tile, entry)
     return tile
+
+
+def bnn_predict_row_tile(layer_sizes, dtype=torch.float32):
+    """Test rows per tile of ``bnn_predict``'s forward launch for this net and dtype (``sgmcmc_bnn_predict_row_tile``:
+    host arithmetic, nothing launched). Performance only; the results do not depend on it."""
+    return _bnn_row_tile("sgmcmc_bnn_predict_row_tile", layer_sizes, dtype)
 
 
 def _bnn_trace_arguments(what, noun, chains, layer_sizes, X):
@@ -572,6 +576,20 @@ def _bnn_trace_arguments(what, noun, chains, layer_sizes, X):
     if X.dim() != 2 or int(X.shape[1]) != sizes[0] or not X.is_contiguous():
         raise ValueError(what + ": X must be a contiguous (N, %d) matrix, got %s" % (sizes[0], tuple(X.shape)))
     return f, mats, sizes, n, ld
+
+
+def _bnn_check_outputs(what, device, outputs):
+    """``outputs``: ``(tensor, dtype, numel, name, required)`` each; a tensor that is given must be one of that dtype holding
+    ``numel`` elements on ``device``."""
+    for out, dt, numel, name, required in outputs:
+        if out is None:
+            if required:
+                raise ValueError("%s: %s is required" % (what, name))
+            continue
+        if not torch.is_tensor(out) or out.dtype != dt:
+            raise TypeError("%s: %s must be a %s tensor" % (what, name, dt))
+        if out.numel() != numel or out.device != device:
+            raise ValueError("%s: %s must hold %d elements on %s" % (what, name, numel, device))
 
 
 def bnn_predict(chains, layer_sizes, X, means, noise_var=None, ens_mean=None, ens_var=None):
@@ -626,19 +644,11 @@ def bnn_score(chains, layer_sizes, X, y, means, row_lppd, row_pwaic, ens_mean, e
     first = mats[0]
     S, N = len(mats) * n, int(X.shape[0])
     f64 = torch.float64
-    for out, dt, numel, name, required in (
-            (y, first.dtype, N, "y", True), (means, first.dtype, S * N, "means", True), (row_lppd, f64, N, "row_lppd", True),
-            (row_pwaic, f64, N, "row_pwaic", True), (ens_mean, f64, N, "ens_mean", True), (ens_var, f64, N, "ens_var", True),
-            (loglik, f64, S * N, "loglik", False), (sample_loglik, f64, S, "sample_loglik", False),
-            (summary, f64, 3, "summary", False)):
-        if out is None:
-            if required:
-                raise ValueError("bnn_score: %s is required" % name)
-            continue
-        if not torch.is_tensor(out) or out.dtype != dt:
-            raise TypeError("bnn_score: %s must be a %s tensor" % (name, dt))
-        if out.numel() != numel or out.device != first.device:
-            raise ValueError("bnn_score: %s must hold %d elements on %s" % (name, numel, first.device))
+    _bnn_check_outputs("bnn_score", first.device, (
+        (y, first.dtype, N, "y", True), (means, first.dtype, S * N, "means", True), (row_lppd, f64, N, "row_lppd", True),
+        (row_pwaic, f64, N, "row_pwaic", True), (ens_mean, f64, N, "ens_mean", True), (ens_var, f64, N, "ens_var", True),
+        (loglik, f64, S * N, "loglik", False), (sample_loglik, f64, S, "sample_loglik", False),
+        (summary, f64, 3, "summary", False)))
     table = (ctypes.c_void_p * len(mats))(*[x.data_ptr() for x in mats])
     with torch.cuda.device(first.device):
         rc = f(table, len(mats), n, ld, (ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, _ptr(X), _ptr(y), N, _ptr(means),
@@ -652,13 +662,7 @@ def bnn_predict_grad_row_tile(sizes, dtype=torch.float32):
     """Test rows per tile of ``bnn_predict_grad``'s forward + backward launch for this net and dtype
     (``sgmcmc_bnn_predict_grad_row_tile``: host arithmetic, nothing launched). Performance only; the results do not depend
     on it."""
-    import ctypes
-    sizes = [int(v) for v in sizes]
-    esize = {torch.float32: 4, torch.float64: 8}[dtype]
-    tile = lib().sgmcmc_bnn_predict_grad_row_tile((ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, esize)
-    if tile < 1:
-        check(tile, "sgmcmc_bnn_predict_grad_row_tile")
-    return tile
+    return _bnn_row_tile("sgmcmc_bnn_predict_grad_row_tile", sizes, dtype)
 
 
 def bnn_predict_grad(chains, layer_sizes, X, means, grads, ens_mean=None, ens_var=None, dmean=None, dvar=None):
@@ -677,18 +681,10 @@ def bnn_predict_grad(chains, layer_sizes, X, means, grads, ens_mean=None, ens_va
     first = mats[0]
     S, N, D0 = len(mats) * n, int(X.shape[0]), sizes[0]
     f64 = torch.float64
-    for out, dt, numel, name, required in (
-            (means, first.dtype, S * N, "means", True), (grads, first.dtype, S * N * D0, "grads", True),
-            (ens_mean, f64, N, "ens_mean", False), (ens_var, f64, N, "ens_var", False),
-            (dmean, f64, N * D0, "dmean", False), (dvar, f64, N * D0, "dvar", False)):
-        if out is None:
-            if required:
-                raise ValueError("bnn_predict_grad: %s is required" % name)
-            continue
-        if not torch.is_tensor(out) or out.dtype != dt:
-            raise TypeError("bnn_predict_grad: %s must be a %s tensor" % (name, dt))
-        if out.numel() != numel or out.device != first.device:
-            raise ValueError("bnn_predict_grad: %s must hold %d elements on %s" % (name, numel, first.device))
+    _bnn_check_outputs("bnn_predict_grad", first.device, (
+        (means, first.dtype, S * N, "means", True), (grads, first.dtype, S * N * D0, "grads", True),
+        (ens_mean, f64, N, "ens_mean", False), (ens_var, f64, N, "ens_var", False),
+        (dmean, f64, N * D0, "dmean", False), (dvar, f64, N * D0, "dvar", False)))
     if len({out is None for out in (ens_mean, ens_var, dmean, dvar)}) != 1:
         raise ValueError("bnn_predict_grad: ens_mean, ens_var, dmean and dvar go together")
     table = (ctypes.c_void_p * len(mats))(*[x.data_ptr() for x in mats])

@@ -133,6 +133,23 @@ def test_build_dependencies_cover_every_file_the_makefile_names():
     assert {"sgmcmc_bnn_gw.hip", "sgmcmc_bnn_cost.hip", "Makefile"} <= have
 
 
+def test_every_internal_header_a_translation_unit_includes_is_a_makefile_dependency():
+    """The objects depend on HDRS and on nothing else: an ``#include "sgmcmc_*.hpp"`` in a ``csrc/*.hip`` that HDRS does not
+    list would leave stale objects in place when that header is edited."""
+    import glob
+    csrc = os.path.join(ROOT, "pysgmcmc_amd", "csrc")
+    text = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
+    hdrs = set(re.search(r"^HDRS\s*:=(.*)$", text, re.M).group(1).split())
+    units = sorted(glob.glob(os.path.join(csrc, "*.hip")))
+    included = {(os.path.basename(u), h) for u in units for h in re.findall(r'#include\s+"(sgmcmc_\w+\.hpp)"', open(u).read())}
+    assert len(units) >= 15 and ("sgmcmc_bnn_predict.hip", "sgmcmc_bnn_small_net.hpp") in included
+    missing = sorted((u, h) for u, h in included if h not in hdrs or not os.path.isfile(os.path.join(csrc, h)))
+    assert not missing, missing
+    # and a header one of those headers includes
+    nested = {h2 for _, h in included for h2 in re.findall(r'#include\s+"(sgmcmc_\w+\.hpp)"', open(os.path.join(csrc, h)).read())}
+    assert nested <= hdrs, sorted(nested - hdrs)
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "pysgmcmc_amd")
     offenders = []
