@@ -52,6 +52,7 @@ PREDICT_ABI_VERSION = 1       # SGMCMC_PREDICT_ABI_VERSION of include/sgmcmc_hip
 CHAINS_ABI_VERSION = 1        # SGMCMC_CHAINS_ABI_VERSION of include/sgmcmc_hip_chains.h (the many-chains diagnostics add-on)
 SCORE_ABI_VERSION = 1         # SGMCMC_SCORE_ABI_VERSION of include/sgmcmc_hip_score.h (the held-out-score add-on)
 PREDICT_GRAD_ABI_VERSION = 1  # SGMCMC_PREDICT_GRAD_ABI_VERSION of include/sgmcmc_hip_predict_grad.h (the predictive-gradient add-on)
+PARTICLES_ABI_VERSION = 1     # SGMCMC_PARTICLES_ABI_VERSION of include/sgmcmc_hip_particles.h (the particle-gradient add-on)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
@@ -261,6 +262,16 @@ def _declare(lib):
         f.restype = _ci
     lib.sgmcmc_bnn_predict_grad_row_tile.argtypes = [ctypes.POINTER(_ci), _ci, _sz]
     lib.sgmcmc_bnn_predict_grad_row_tile.restype = _ci
+    # include/sgmcmc_hip_particles.h: theta, n_particles, ld, layer sizes, n_layers, Xb, ldx, yb, batch, batch_size, n_examples,
+    # wdecay, prior_mean, prior_var, add_prior, grad, ld_grad, cost_out, stream
+    lib.sgmcmc_particles_abi_version.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_bnn_particles_cost_grad_" + sfx)
+        f.argtypes = ([_vp, _sz, _sz, ctypes.POINTER(_ci), _ci, _vp, _sz, _vp, _ci] + [ctypes.c_double] * 5
+                      + [_ci, _vp, _sz, _vp, _vp])
+        f.restype = _ci
+    lib.sgmcmc_bnn_particles_lds_bytes.argtypes = [ctypes.POINTER(_ci), _ci, _ci, _sz]
+    lib.sgmcmc_bnn_particles_lds_bytes.restype = _sz
 
 
 def lib():
@@ -293,6 +304,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: held-out-score add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_predict_grad_abi_version() != PREDICT_GRAD_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: predictive-gradient add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_particles_abi_version() != PARTICLES_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: particle-gradient add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

@@ -18,7 +18,7 @@ __all__ = [
     "LaunchConfig", "KernelEvents", "StepOpts", "step_stats_records", "step_scalars", "toy_chains", "set_launch_config", "get_launch_config", "summary_workspace", "counter_add", "StepStats", "bnn_head", "bnn_dense_tanh_backward", "bnn_dense_tanh_backward_fits", "colsum_finish", "tanh_backward", "tanh_backward_colsum", "bnn_last_layer_backward", "bnn_fused_sghmc_steps", "step_stats_finish",
     "bnn_fused_sgld_steps", "bnn_fused_rsghmc_steps", "bnn_fused_steps", "step_scalars_table", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
     "ess_variogram", "bnn_predict", "bnn_predict_row_tile", "chain_diag", "bnn_score",
-    "bnn_predict_grad", "bnn_predict_grad_row_tile",
+    "bnn_predict_grad", "bnn_predict_grad_row_tile", "bnn_particles_cost_grad", "bnn_particles_lds_bytes",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -693,6 +693,56 @@ def bnn_predict_grad(chains, layer_sizes, X, means, grads, ens_mean=None, ens_va
                _ptr(grads), _ptr(ens_mean), _ptr(ens_var), _ptr(dmean), _ptr(dvar), _stream(first))
     check(rc, "sgmcmc_bnn_predict_grad")
     return grads
+
+
+def bnn_particles_lds_bytes(layer_sizes, batch, dtype=torch.float32):
+    """Dynamic LDS of one workgroup of ``bnn_particles_cost_grad`` for this net, minibatch and dtype, in bytes
+    (``sgmcmc_bnn_particles_lds_bytes``: the whole-step kernel's footprint rule; host arithmetic, nothing launched), or 0
+    when the kernel does not take the call: the footprint exceeds 160 KiB, or the net is none it runs."""
+    import ctypes
+    sizes = [int(v) for v in layer_sizes]
+    esize = {torch.float32: 4, torch.float64: 8}[dtype]
+    if len(sizes) < 2:
+        return 0
+    return int(lib().sgmcmc_bnn_particles_lds_bytes((ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, int(batch), esize))
+
+
+def bnn_particles_cost_grad(theta, n, ld, layer_sizes, Xb, yb, grad, ld_grad, costs, batch_size, n_examples, wdecay,
+                            prior_mean, prior_var, add_prior=True):
+    """K15 (``include/sgmcmc_hip_particles.h``): the cost of each of ``n`` particles of a small tanh-MLP BNN on one
+    minibatch and its gradient with respect to the particle's parameters, in one launch without host synchronisation.
+
+    ``theta``: flat device tensor, particle ``p`` the ``n_params`` elements from ``p * ld`` on, in the whole-step kernel's
+    parameter order, at any alignment. ``Xb``: ``(B, layer_sizes[0])`` of that dtype with dense rows, possibly a pitched
+    view (``ldx = Xb.stride(0)``); ``yb``: its ``B`` targets, contiguous. ``grad``: flat, row ``p`` written from
+    ``p * ld_grad`` on, nothing behind ``n_params``; ``costs``: ``n`` elements. ``add_prior=False`` leaves the weight-prior
+    term ``coef * theta`` out, which gives the gradient row of the whole-step kernel. Returns ``costs``."""
+    import ctypes
+    sizes = [int(v) for v in layer_sizes]
+    what = "bnn_particles_cost_grad"
+    if len(sizes) < 2:
+        raise ValueError(what + ": layer_sizes needs at least two entries")
+    n, ld, ld_grad, n_params = int(n), int(ld), int(ld_grad), _bnn_n_params(sizes)
+    f = getattr(lib(), "sgmcmc_bnn_particles_cost_grad_" + _sfx(theta))
+    for t, name in ((Xb, "Xb"), (yb, "yb"), (grad, "grad"), (costs, "costs")):
+        if not torch.is_tensor(t) or t.dtype != theta.dtype or t.device != theta.device:
+            raise TypeError("%s: %s must be a %s tensor on %s" % (what, name, theta.dtype, theta.device))
+    if Xb.dim() != 2 or int(Xb.shape[1]) != sizes[0] or (sizes[0] > 1 and Xb.stride(1) != 1):
+        raise ValueError("%s: Xb must be a (B, %d) matrix with dense rows, got %s" % (what, sizes[0], tuple(Xb.shape)))
+    B = int(Xb.shape[0])
+    ldx = int(Xb.stride(0)) if B > 1 else max(int(Xb.stride(0)), sizes[0])
+    if yb.numel() != B:
+        raise ValueError("%s: yb must hold the %d targets of Xb" % (what, B))
+    if n > 0 and (theta.numel() < (n - 1) * ld + n_params or grad.numel() < (n - 1) * ld_grad + n_params
+                  or costs.numel() < n or min(ld, ld_grad) < n_params):
+        raise ValueError("%s: theta, grad or costs is too short for %d particles of %d parameters at pitches %d and %d"
+                         % (what, n, n_params, ld, ld_grad))
+    with _on(theta):
+        rc = f(_ptr(theta), n, ld, (ctypes.c_int * len(sizes))(*sizes), len(sizes) - 1, Xb.data_ptr(), ldx, _ptr(yb), B,
+               float(batch_size), float(n_examples), float(wdecay), float(prior_mean), float(prior_var), int(bool(add_prior)),
+               _ptr(grad), ld_grad, _ptr(costs), _stream(theta))
+    check(rc, "sgmcmc_bnn_particles_cost_grad")
+    return costs
 
 
 def summary_workspace(device):

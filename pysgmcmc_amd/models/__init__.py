@@ -2,14 +2,17 @@
 abstract model interface of ``models/base_model.py`` is outside the sampler path; its two normalisation
 helpers live in ``bayesian_neural_network``), and, beyond the reference, ``posterior_predictive``, ``heldout_score`` and
 ``predictive_gradients``: the predictive moments of device traces, their score against held-out targets, and their gradients
-with respect to the inputs, each in one device call."""
+with respect to the inputs, each in one device call; and ``BNNParticleCost`` / ``bnn_particles``: the BNN cost on flat particles for
+particle samplers, whose costs and parameter gradients come from one kernel launch."""
 from pysgmcmc_amd.models.bayesian_neural_network import (
     BayesianNeuralNetwork,
     log_variance_prior_log_like,
     weight_prior_log_like,
 )
+from pysgmcmc_amd.models.particles import BNNParticleCost, bnn_particles
 from pysgmcmc_amd.models.predictive import PredictiveGradients, posterior_predictive, predictive_gradients
 from pysgmcmc_amd.models.scoring import HeldOutScore, heldout_score
 
 __all__ = ("BayesianNeuralNetwork", "log_variance_prior_log_like", "weight_prior_log_like", "posterior_predictive",
-           "heldout_score", "HeldOutScore", "predictive_gradients", "PredictiveGradients")
+           "heldout_score", "HeldOutScore", "predictive_gradients", "PredictiveGradients", "BNNParticleCost",
+           "bnn_particles")

@@ -39,7 +39,9 @@ class SVGDSampler(MCMCSampler):
         with the attribute ``batched = True`` is instead called once with the ``[n, d]``
         matrix of all particles and must return the ``n`` costs (one backward pass for all
         particles instead of ``n``). A plain per-particle cost is batched automatically with
-        ``torch.func.vmap`` when that reproduces the particle-by-particle costs and gradients.
+        ``torch.func.vmap`` when that reproduces the particle-by-particle costs and gradients. A cost that brings
+        ``particles_cost_and_grad`` (``models.BNNParticleCost``) gives costs and gradients of all particles in one
+        kernel launch without autograd, whenever the call fits the kernel and ``cost_fun.use_hip_kernel`` is set.
     alpha, fudge_factor : float
         Decay of the running mean of squared updates and the constant added to its square
         root (``svgd.py:129-137``; AdaGrad with momentum, as in Liu & Wang's code).
@@ -109,6 +111,9 @@ class SVGDSampler(MCMCSampler):
     # cost differentiates the [n, d] matrix in one pass, and a plain per-particle cost is batched with
     # torch.func.vmap when that reproduces the loop's costs and gradients on the first step
     def _cost_and_grad(self):
+        launch = getattr(self._particle_cost_fun, "particles_cost_and_grad", None)
+        if launch is not None and self._particles_kernel_fits():
+            return self._cost_and_grad_particles(launch)
         if self._batched:
             return self._cost_and_grad_matrix(self.cost_fun)
         if self._vmapped is None:
@@ -116,6 +121,36 @@ class SVGDSampler(MCMCSampler):
         if self._vmapped:
             return self._cost_and_grad_matrix(self._vmapped)
         return super()._cost_and_grad()
+
+    # a particle cost that brings `particles_cost_and_grad` (models.BNNParticleCost: kernel K15, csrc/sgmcmc_bnn_particles.hip)
+    # gives the costs and the gradients of ALL particles in one launch, read from the arena's theta row and written into its
+    # grad row: no autograd graph, no requires_grad on the particle matrix. Any other cost never reaches these two methods.
+    _particle_costs = None
+
+    def _particles_kernel_fits(self):
+        cost = self._particle_cost_fun
+        if not getattr(cost, "use_hip_kernel", False) or self.device.type != "cuda":
+            return False
+        X, Y = cost.x_placeholder.value, cost.y_placeholder.value
+        dt = self._torch_dtype
+        if not (torch.is_tensor(X) and torch.is_tensor(Y) and X.is_cuda and Y.is_cuda and X.dtype == dt and Y.dtype == dt):
+            return False
+        if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1) or Y.numel() != X.shape[0] or not Y.is_contiguous():
+            return False
+        return cost.n_params == self.particle_dim and cost.fits(dt, int(X.shape[0]))
+
+    def _cost_and_grad_particles(self, launch):
+        if self._particle_costs is None:
+            self._particle_costs = torch.empty(self.n_particles, dtype=self._torch_dtype, device=self.device)
+        self._grad_decay = 0.0
+        with torch.no_grad():
+            costs = launch(self.arena.row("theta"), self.arena.row("grad"), self.n_particles, self.particle_pitch,
+                           self._particle_costs)
+        # the graph modes hand out their static cost tensor, as with any cost; an eager step whose costs stay on the device
+        # gets a tensor of its own, which the next step does not overwrite
+        if not self.use_hip_graph and self.sample_format != "numpy":
+            return costs.clone()
+        return costs
 
     def _cost_and_grad_matrix(self, fun):
         self._grad_decay = 0.0
