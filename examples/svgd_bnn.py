@@ -2,7 +2,12 @@
 and the parameter gradients of all particles come from one launch of kernel K15 per step (`BNNParticleCost`), the update from
 the SVGD kernels. The particle matrix `sampler.particles` is an (n, P) device matrix of flat parameter rows, which is what
 `models.posterior_predictive` and `models.heldout_score` read: particles -> predict -> score never leaves the device, and no
-parameter is copied to the host; only the printed numbers are."""
+parameter is copied to the host; only the printed numbers are.
+
+    python examples/svgd_bnn.py [--particles N] [--steps K]
+
+Up to 128 particles step on the register-resident SVGD kernels, 129 .. 1024 (e.g. ``--particles 512``) on the tiled ones."""
+import argparse
 import os
 import sys
 
@@ -17,7 +22,11 @@ from pysgmcmc_amd.samplers import SVGDSampler
 from pysgmcmc_amd.stepsize_schedules import ConstantStepsizeSchedule
 
 device, dtype = torch.device("cuda:0"), torch.float32
-layer_sizes, n_particles, n_steps = [1, 50, 50, 50, 1], 16, 3000
+parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+parser.add_argument("--particles", type=int, default=16, help="number of particles, 1 .. 1024 (default 16)")
+parser.add_argument("--steps", type=int, default=3000, help="number of SVGD steps (default 3000)")
+args = parser.parse_args()
+layer_sizes, n_particles, n_steps = [1, 50, 50, 50, 1], args.particles, args.steps
 
 rng = np.random.RandomState(1)
 X = rng.rand(100, 1)

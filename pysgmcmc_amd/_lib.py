@@ -53,6 +53,7 @@ CHAINS_ABI_VERSION = 1        # SGMCMC_CHAINS_ABI_VERSION of include/sgmcmc_hip_
 SCORE_ABI_VERSION = 1         # SGMCMC_SCORE_ABI_VERSION of include/sgmcmc_hip_score.h (the held-out-score add-on)
 PREDICT_GRAD_ABI_VERSION = 1  # SGMCMC_PREDICT_GRAD_ABI_VERSION of include/sgmcmc_hip_predict_grad.h (the predictive-gradient add-on)
 PARTICLES_ABI_VERSION = 1     # SGMCMC_PARTICLES_ABI_VERSION of include/sgmcmc_hip_particles.h (the particle-gradient add-on)
+SVGD_MANY_ABI_VERSION = 1     # SGMCMC_SVGD_MANY_ABI_VERSION of include/sgmcmc_hip_svgd_many.h (SVGD with up to 1024 particles)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
@@ -272,6 +273,20 @@ def _declare(lib):
         f.restype = _ci
     lib.sgmcmc_bnn_particles_lds_bytes.argtypes = [ctypes.POINTER(_ci), _ci, _ci, _sz]
     lib.sgmcmc_bnn_particles_lds_bytes.restype = _sz
+    # include/sgmcmc_hip_svgd_many.h: the argument lists of sgmcmc_svgd_step_* / sgmcmc_svgd_kernel_* above
+    lib.sgmcmc_svgd_many_abi_version.restype = _ci
+    lib.sgmcmc_svgd_many_max_particles.restype = _ci
+    lib.sgmcmc_svgd_many_workspace_bytes.argtypes = [_sz, _sz]
+    lib.sgmcmc_svgd_many_workspace_bytes.restype = _sz
+    lib.sgmcmc_svgd_many_plan.argtypes = [_sz, _sz, _sz, ctypes.POINTER(_ci), _ci]
+    lib.sgmcmc_svgd_many_plan.restype = _ci
+    for sfx, real in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        f = getattr(lib, "sgmcmc_svgd_many_step_" + sfx)
+        f.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, real, ctypes.c_double, real, _ci, _vp, _vp]
+        f.restype = _ci
+        f = getattr(lib, "sgmcmc_svgd_many_kernel_" + sfx)
+        f.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _vp]
+        f.restype = _ci
 
 
 def lib():
@@ -306,6 +321,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: predictive-gradient add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_particles_abi_version() != PARTICLES_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: particle-gradient add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_svgd_many_abi_version() != SVGD_MANY_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: many-particle SVGD add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

@@ -8,6 +8,9 @@ device memory and streams only.
 
 No CPU path exists: a CPU tensor raises ``SgmcmcLibraryError``.
 """
+import collections
+import ctypes
+
 import torch
 
 from pysgmcmc_amd._lib import SgmcmcLibraryError, check, lib
@@ -19,6 +22,7 @@ __all__ = [
     "bnn_fused_sgld_steps", "bnn_fused_rsghmc_steps", "bnn_fused_steps", "step_scalars_table", "window_gather", "tanh_rowdot", "bias_tanh", "bnn_dense_tanh", "bnn_dense_tanh_fits", "bnn_head_last_layer_backward", "svgd_workspace", "svgd_step", "svgd_kernel", "svgd_max_particles",
     "ess_variogram", "bnn_predict", "bnn_predict_row_tile", "chain_diag", "bnn_score",
     "bnn_predict_grad", "bnn_predict_grad_row_tile", "bnn_particles_cost_grad", "bnn_particles_lds_bytes",
+    "svgd_many_max_particles", "svgd_many_workspace", "svgd_many_step", "svgd_many_kernel", "svgd_many_plan",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -1221,4 +1225,68 @@ def svgd_kernel(particles, n_particles, dim, workspace, ld=None, kernel_gradient
         rc = f(_ptr(particles), n, int(dim), ld, _ptr(workspace), _ptr(K), _ptr(kg), int(dim), _ptr(bw),
                _stream(particles))
     check(rc, "sgmcmc_svgd_kernel")
+    return K, kg, bw
+
+
+# ---- SVGD with up to 1024 particles (include/sgmcmc_hip_svgd_many.h, csrc/sgmcmc_svgd_many.hip) ----
+SvgdManyLaunch = collections.namedtuple("SvgdManyLaunch", "id tile grid cap")
+SVGD_MANY_IDS = {1: "gram", 2: "reduce", 3: "dist", 4: "select", 5: "next", 6: "bandwidth", 7: "kmatrix", 8: "update",
+                 9: "kgrad", 10: "copy", 11: "mean"}
+
+
+def svgd_many_max_particles():
+    return int(lib().sgmcmc_svgd_many_max_particles())
+
+
+def svgd_many_workspace(n_particles, like):
+    """Device workspace of the many-particle SVGD kernels for ``n_particles`` particles in ``like``'s dtype/device."""
+    nbytes = int(lib().sgmcmc_svgd_many_workspace_bytes(int(n_particles), like.element_size()))
+    if nbytes == 0:
+        raise ValueError("pysgmcmc_amd: the many-particle SVGD path supports 2..%d particles in float32/float64, got %d"
+                         % (svgd_many_max_particles(), n_particles))
+    if not like.is_cuda:
+        _ptr(like)                       # raises the no-CPU-path error
+    return torch.empty(nbytes // like.element_size(), dtype=like.dtype, device=like.device)
+
+
+def svgd_many_plan(n_particles, dim, like):
+    """The launches of one ``svgd_many_step`` call: a list of ``SvgdManyLaunch(id, tile, grid, cap)`` (host arithmetic;
+    ``like`` is a tensor or a dtype and gives the element size)."""
+    esize = like.element_size() if torch.is_tensor(like) else torch.empty((), dtype=like).element_size()
+    k = int(lib().sgmcmc_svgd_many_plan(int(n_particles), int(dim), esize, None, 0))
+    check(0 if k > 0 else k, "sgmcmc_svgd_many_plan")
+    out = (ctypes.c_int * (4 * k))()
+    lib().sgmcmc_svgd_many_plan(int(n_particles), int(dim), esize, out, 4 * k)
+    return [SvgdManyLaunch(*out[4 * i:4 * i + 4]) for i in range(k)]
+
+
+def svgd_many_step(particles, grad, hist_grad, n_particles, dim, eps, alpha, fudge_factor, workspace, ld=None,
+                   repulsion_sign=1):
+    """One SVGD step in place on the ``[n_particles x ld]`` matrices (``sgmcmc_svgd_many_step_*``, 2..1024 particles)."""
+    f = getattr(lib(), "sgmcmc_svgd_many_step_" + _sfx(particles))
+    ld = int(dim if ld is None else ld)
+    for t in (particles, grad, hist_grad):
+        if t.numel() < (n_particles - 1) * ld + dim:
+            raise ValueError("pysgmcmc_amd: SVGD matrix shorter than (n_particles - 1) * ld + dim")
+    with _on(particles):
+        rc = f(_ptr(particles), _ptr(grad), _ptr(hist_grad), int(n_particles), int(dim), ld, float(eps), float(alpha),
+               float(fudge_factor), int(repulsion_sign), _ptr(workspace), _stream(particles))
+    check(rc, "sgmcmc_svgd_many_step")
+
+
+def svgd_many_kernel(particles, n_particles, dim, workspace, ld=None, kernel_gradients=True):
+    """``svgd_kernel`` for 2..1024 particles: (kernel_matrix [n, n], kernel_gradients [n, dim] or None, bandwidth tensor
+    {median, h, h^2}) as fresh device tensors."""
+    f = getattr(lib(), "sgmcmc_svgd_many_kernel_" + _sfx(particles))
+    ld = int(dim if ld is None else ld)
+    n = int(n_particles)
+    if particles.numel() < (n - 1) * ld + dim:
+        raise ValueError("pysgmcmc_amd: SVGD matrix shorter than (n_particles - 1) * ld + dim")
+    K = torch.empty((n, n), dtype=particles.dtype, device=particles.device)
+    kg = torch.empty((n, int(dim)), dtype=particles.dtype, device=particles.device) if kernel_gradients else None
+    bw = torch.empty(3, dtype=particles.dtype, device=particles.device)
+    with _on(particles):
+        rc = f(_ptr(particles), n, int(dim), ld, _ptr(workspace), _ptr(K), _ptr(kg), int(dim), _ptr(bw),
+               _stream(particles))
+    check(rc, "sgmcmc_svgd_many_kernel")
     return K, kg, bw

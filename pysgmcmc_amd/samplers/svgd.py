@@ -193,16 +193,34 @@ class SVGDSampler(MCMCSampler):
         flat = self.arena.row(row)
         return torch.as_strided(flat, (self.n_particles, self.particle_dim), (self.particle_pitch, 1))
 
+    # up to kernels.svgd_max_particles() (128) particles the step keeps K and a column tile in registers or LDS
+    # (csrc/sgmcmc_svgd.hip); above, up to kernels.svgd_many_max_particles() (1024), the tiled kernels of
+    # csrc/sgmcmc_svgd_many.hip run: the same arguments, the same arithmetic contract, a workspace of their own
+    @staticmethod
+    def _many(n):
+        return n > kernels.svgd_max_particles()
+
+    @staticmethod
+    def _workspace_for(n, like):
+        if not SVGDSampler._many(n):
+            return kernels.svgd_workspace(n, like)
+        if n > kernels.svgd_many_max_particles():
+            raise ValueError("pysgmcmc_amd: SVGD supports up to %d particles (%d in the register-resident kernels, %d in "
+                             "the tiled ones), got %d" % (kernels.svgd_many_max_particles(), kernels.svgd_max_particles(),
+                                                          kernels.svgd_many_max_particles(), n))
+        return kernels.svgd_many_workspace(n, like)
+
     def _ws(self):
         if self._workspace is None:
-            self._workspace = kernels.svgd_workspace(self.n_particles, self.arena.row("theta"))
+            self._workspace = self._workspace_for(self.n_particles, self.arena.row("theta"))
         return self._workspace
 
     def _kernel_step(self, eps, xi):
         a = self.arena
-        kernels.svgd_step(a.row("theta"), a.row("grad"), a.row("historical_grad"),
-                          self.n_particles, self.particle_dim, eps, self.alpha, self.fudge_factor,
-                          self._ws(), ld=self.particle_pitch, repulsion_sign=self.repulsion_sign)
+        step = kernels.svgd_many_step if self._many(self.n_particles) else kernels.svgd_step
+        step(a.row("theta"), a.row("grad"), a.row("historical_grad"),
+             self.n_particles, self.particle_dim, eps, self.alpha, self.fudge_factor,
+             self._ws(), ld=self.particle_pitch, repulsion_sign=self.repulsion_sign)
 
     def svgd_kernel(self, particles=None):
         """Kernel matrix and summed kernel gradients of the current particles (``svgd.py:149-181``):
@@ -216,7 +234,8 @@ class SVGDSampler(MCMCSampler):
             x = torch.as_tensor(particles).to(device=self.device, dtype=self._torch_dtype).contiguous()
             assert x.dim() == 2, "svgd_kernel: a 2-d tensor must be passed."
             n, d = int(x.shape[0]), int(x.shape[1])
-            ws = kernels.svgd_workspace(n, x)
-        K, kg, bw = kernels.svgd_kernel(x.reshape(-1), n, d, ws, ld=ld)
+            ws = self._workspace_for(n, x)
+        kernel = kernels.svgd_many_kernel if self._many(n) else kernels.svgd_kernel
+        K, kg, bw = kernel(x.reshape(-1), n, d, ws, ld=ld)
         self.bandwidth = bw
         return K, kg
