@@ -54,6 +54,7 @@ SCORE_ABI_VERSION = 1         # SGMCMC_SCORE_ABI_VERSION of include/sgmcmc_hip_s
 PREDICT_GRAD_ABI_VERSION = 1  # SGMCMC_PREDICT_GRAD_ABI_VERSION of include/sgmcmc_hip_predict_grad.h (the predictive-gradient add-on)
 PARTICLES_ABI_VERSION = 1     # SGMCMC_PARTICLES_ABI_VERSION of include/sgmcmc_hip_particles.h (the particle-gradient add-on)
 SVGD_MANY_ABI_VERSION = 1     # SGMCMC_SVGD_MANY_ABI_VERSION of include/sgmcmc_hip_svgd_many.h (SVGD with up to 1024 particles)
+KSD_ABI_VERSION = 1           # SGMCMC_KSD_ABI_VERSION of include/sgmcmc_hip_ksd.h (the kernel Stein discrepancy, K16)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
@@ -287,6 +288,18 @@ def _declare(lib):
         f = getattr(lib, "sgmcmc_svgd_many_kernel_" + sfx)
         f.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _vp]
         f.restype = _ci
+    # include/sgmcmc_hip_ksd.h: samples, ld_x, scores, ld_s, n, dim, kind, c, beta, h2, workspace, matrix_out, ld_m,
+    # row_sums_out, stats_out, stream
+    lib.sgmcmc_ksd_abi_version.restype = _ci
+    lib.sgmcmc_ksd_max_samples.restype = _ci
+    lib.sgmcmc_ksd_workspace_bytes.argtypes = [_sz, _sz]
+    lib.sgmcmc_ksd_workspace_bytes.restype = _sz
+    lib.sgmcmc_ksd_plan.argtypes = [_sz, _sz, _sz, ctypes.POINTER(_ci), _ci]
+    lib.sgmcmc_ksd_plan.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_ksd_" + sfx)
+        f.argtypes = [_vp, _sz, _vp, _sz, _sz, _sz, _ci] + [ctypes.c_double] * 3 + [_vp, _vp, _sz, _vp, _vp, _vp]
+        f.restype = _ci
 
 
 def lib():
@@ -323,6 +336,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: particle-gradient add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_svgd_many_abi_version() != SVGD_MANY_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: many-particle SVGD add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_ksd_abi_version() != KSD_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: kernel Stein discrepancy add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

@@ -23,6 +23,7 @@ __all__ = [
     "ess_variogram", "bnn_predict", "bnn_predict_row_tile", "chain_diag", "bnn_score",
     "bnn_predict_grad", "bnn_predict_grad_row_tile", "bnn_particles_cost_grad", "bnn_particles_lds_bytes",
     "svgd_many_max_particles", "svgd_many_workspace", "svgd_many_step", "svgd_many_kernel", "svgd_many_plan",
+    "ksd_max_samples", "ksd_workspace", "ksd_plan", "ksd",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -1290,3 +1291,81 @@ def svgd_many_kernel(particles, n_particles, dim, workspace, ld=None, kernel_gra
                _stream(particles))
     check(rc, "sgmcmc_svgd_many_kernel")
     return K, kg, bw
+
+
+# ---- K16: kernel Stein discrepancy of up to 4096 samples (include/sgmcmc_hip_ksd.h, csrc/sgmcmc_ksd.hip) ----
+KsdLaunch = collections.namedtuple("KsdLaunch", "id tile grid cap")
+KSD_IDS = {1: "mean", 2: "gram", 3: "reduce", 4: "pair", 5: "finish"}
+KSD_KINDS = {"imq": 0, "rbf": 1}
+
+
+def ksd_max_samples():
+    return int(lib().sgmcmc_ksd_max_samples())
+
+
+def ksd_workspace(n, like):
+    """Device workspace of ``ksd`` for ``n`` samples in ``like``'s dtype/device; it does not depend on the width."""
+    nbytes = int(lib().sgmcmc_ksd_workspace_bytes(int(n), like.element_size()))
+    if nbytes == 0:
+        raise ValueError("pysgmcmc_amd: the kernel Stein discrepancy supports 2..%d samples in float32/float64, got %d"
+                         % (ksd_max_samples(), n))
+    if not like.is_cuda:
+        _ptr(like)                       # raises the no-CPU-path error
+    return torch.empty(nbytes // like.element_size(), dtype=like.dtype, device=like.device)
+
+
+def ksd_plan(n, dim, like):
+    """The launches of one ``ksd`` call: a list of ``KsdLaunch(id, tile, grid, cap)`` (host arithmetic; ``like`` is a tensor
+    or a dtype and gives the element size)."""
+    esize = like.element_size() if torch.is_tensor(like) else torch.empty((), dtype=like).element_size()
+    k = int(lib().sgmcmc_ksd_plan(int(n), int(dim), esize, None, 0))
+    check(0 if k > 0 else k, "sgmcmc_ksd_plan")
+    out = (ctypes.c_int * (4 * k))()
+    lib().sgmcmc_ksd_plan(int(n), int(dim), esize, out, 4 * k)
+    return [KsdLaunch(*out[4 * i:4 * i + 4]) for i in range(k)]
+
+
+def ksd(samples, scores, workspace, kind="imq", c=1.0, beta=-0.5, h2=None, matrix=None, row_sums=None, stats=None):
+    """K16 (``sgmcmc_ksd_*``): the Stein kernel matrix of the ``(n, dim)`` device matrices ``samples`` and ``scores`` (dense
+    rows, any row pitch) and its sums, on the current stream without host synchronisation. ``kind``: ``"imq"``
+    (``(c^2 + r^2)^beta``) or ``"rbf"`` (``exp(-r^2 / (2 h2))``, ``h2`` required). ``matrix``: ``(n, n)`` of the samples'
+    dtype with dense rows, or None; ``row_sums``: ``n`` float64, or None; ``stats``: 4 float64 ``{V, U, total, trace}``,
+    allocated when None. Returns ``stats``."""
+    what = "ksd"
+    f = getattr(lib(), "sgmcmc_ksd_" + _sfx(samples))
+    if kind not in KSD_KINDS:
+        raise ValueError("%s: kind must be 'imq' or 'rbf', got %r" % (what, kind))
+    if kind == "rbf" and h2 is None:
+        raise ValueError("%s: the RBF kernel needs h2" % what)
+    if not torch.is_tensor(scores) or scores.dtype != samples.dtype or scores.device != samples.device:
+        raise TypeError("%s: scores must be a %s tensor on %s" % (what, samples.dtype, samples.device))
+    if samples.dim() != 2 or scores.shape != samples.shape:
+        raise ValueError("%s: samples and scores must be (n, dim) matrices of one shape" % what)
+    n, dim = int(samples.shape[0]), int(samples.shape[1])
+    for t, name in ((samples, "samples"), (scores, "scores")):
+        if (dim > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < dim):
+            raise ValueError("%s: %s must have dense rows that do not overlap" % (what, name))
+    if not samples.is_cuda:
+        _ptr(samples)                    # raises the no-CPU-path error
+    need = int(lib().sgmcmc_ksd_workspace_bytes(n, samples.element_size()))
+    if need and (not torch.is_tensor(workspace) or workspace.numel() * workspace.element_size() < need):
+        raise ValueError("%s: the workspace is shorter than ksd_workspace(%d, samples): %d bytes" % (what, n, need))
+    ld_x, ld_s = (int(t.stride(0)) if n > 1 else dim for t in (samples, scores))
+    ld_m = 0
+    if matrix is not None:
+        if matrix.dtype != samples.dtype or matrix.device != samples.device or tuple(matrix.shape) != (n, n) \
+                or matrix.stride(1) != 1 or matrix.stride(0) < n:
+            raise ValueError("%s: matrix must be (n, n) of the samples' dtype with dense rows that do not overlap" % what)
+        ld_m = int(matrix.stride(0))
+    for t, name, size in ((row_sums, "row_sums", n), (stats, "stats", 4)):
+        if t is not None and (t.dtype != torch.float64 or t.device != samples.device or t.numel() != size
+                              or not t.is_contiguous()):
+            raise ValueError("%s: %s must be %d contiguous float64 elements on %s" % (what, name, size, samples.device))
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.float64, device=samples.device)
+    with torch.cuda.device(samples.device):
+        rc = f(samples.data_ptr(), ld_x, scores.data_ptr(), ld_s, n, dim, KSD_KINDS[kind], float(c), float(beta),
+               float(0.0 if h2 is None else h2), _ptr(workspace), None if matrix is None else matrix.data_ptr(), ld_m,
+               _ptr(row_sums), _ptr(stats), _stream(samples))
+    check(rc, "sgmcmc_ksd")
+    return stats

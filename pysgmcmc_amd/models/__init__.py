@@ -3,7 +3,8 @@ abstract model interface of ``models/base_model.py`` is outside the sampler path
 helpers live in ``bayesian_neural_network``), and, beyond the reference, ``posterior_predictive``, ``heldout_score`` and
 ``predictive_gradients``: the predictive moments of device traces, their score against held-out targets, and their gradients
 with respect to the inputs, each in one device call; and ``BNNParticleCost`` / ``bnn_particles``: the BNN cost on flat particles for
-particle samplers, whose costs and parameter gradients come from one kernel launch."""
+particle samplers, whose costs and parameter gradients come from one kernel launch; and ``bnn_posterior_scores``: the
+posterior's score at every row of a trace from that kernel, for ``diagnostics.stein``."""
 from pysgmcmc_amd.models.bayesian_neural_network import (
     BayesianNeuralNetwork,
     log_variance_prior_log_like,
@@ -11,8 +12,9 @@ from pysgmcmc_amd.models.bayesian_neural_network import (
 )
 from pysgmcmc_amd.models.particles import BNNParticleCost, bnn_particles
 from pysgmcmc_amd.models.predictive import PredictiveGradients, posterior_predictive, predictive_gradients
+from pysgmcmc_amd.models.scores import bnn_posterior_scores
 from pysgmcmc_amd.models.scoring import HeldOutScore, heldout_score
 
 __all__ = ("BayesianNeuralNetwork", "log_variance_prior_log_like", "weight_prior_log_like", "posterior_predictive",
            "heldout_score", "HeldOutScore", "predictive_gradients", "PredictiveGradients", "BNNParticleCost",
-           "bnn_particles")
+           "bnn_particles", "bnn_posterior_scores")

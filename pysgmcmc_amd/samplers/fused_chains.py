@@ -161,6 +161,39 @@ class FusedBNNChains(object):
             X = torch.as_tensor(np.asarray(X), dtype=self.storage.dtype, device=self.storage.device)
         return predictive_gradients(trace, X, self.samplers[0]._bnn_layer_sizes(), **kw)
 
+    def posterior_scores(self, trace, **kw):
+        """``grad log p(theta | X, y)`` at every row of ``trace`` (what :meth:`collect` returns, or an ``(n, P)`` matrix),
+        from the group's own resident data set and cost constants: ``models.bnn_posterior_scores``, K15 without
+        autograd. Returns ``(rows, P)`` with the chains flattened."""
+        from pysgmcmc_amd.models.scores import bnn_posterior_scores
+        first = self.samplers[0]
+        gen, cost = first.batch_generator, first.cost_fun
+        return bnn_posterior_scores(trace, first._bnn_layer_sizes(), gen.x_dev, gen.y_dev, wdecay=cost.wdecay,
+                                    prior_mean=cost.prior_mean, prior_var=cost.prior_var, **kw)
+
+    def stein_discrepancy(self, trace, **kw):
+        """Kernel Stein discrepancy of the samples in ``trace`` (what :meth:`collect` returns, or an ``(n, P)`` matrix)
+        against the posterior of the group's own data set: the scores from :meth:`posterior_scores`, then
+        ``diagnostics.kernel_stein_discrepancy(samples, scores, **kw)`` (kernel K16). Unlike R-hat and ESS it sees the bias
+        of the chains' stationary distribution at their stepsize. A trace of more than 4096 rows in all is thinned evenly
+        (every ``k``-th sample of every chain, ``k`` the smallest that fits) and the result's ``thinning`` is that ``k``.
+        Returns a ``diagnostics.SteinDiscrepancy`` of device tensors; nothing waits for the host."""
+        from pysgmcmc_amd.diagnostics.stein import MAX_SAMPLES, kernel_stein_discrepancy
+        if not torch.is_tensor(trace):
+            trace = trace.values()
+        x = trace if trace.dim() == 3 else trace.unsqueeze(0)
+        m, n = int(x.shape[0]), int(x.shape[1])
+        if m > MAX_SAMPLES:
+            raise ValueError("FusedBNNChains.stein_discrepancy: %d chains, the limit is %d samples in all" % (m, MAX_SAMPLES))
+        k = 1
+        while m * len(range(0, n, k)) > MAX_SAMPLES:
+            k += 1
+        if k > 1:
+            x = x[:, ::k]
+        x = x.reshape(-1, x.shape[-1])
+        out = kernel_stein_discrepancy(x, self.posterior_scores(x), **kw)
+        return out._replace(thinning=k)
+
     @classmethod
     def for_dataset(cls, X, y, n_chains, hidden=(50, 50, 50), batch_size=20, seed=0, dtype=torch.float32,
                     device="cuda:0", stepsize=0.01, burn_in_steps=1000, mdecay=0.05, init_seed=None):
