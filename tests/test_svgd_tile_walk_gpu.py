@@ -142,15 +142,21 @@ def step_reference(case, wide=np.float64):
     grad_theta (svgd.py:124-127, 176-181), so u * S is the scale of its rounding error whatever the order of summation;
     J = 1 / (fudge + sqrt(h_new)) bounds |d adj / d grad_theta| (the second term of that derivative has the opposite sign
     and is smaller, since (1 - alpha) gt^2 <= h_new)."""
-    X, G, H = inputs(case)
+    return step_reference_on(inputs(case), case.sign, wide)
+
+
+def step_reference_on(xgh, sign, wide=np.float64):
+    """``step_reference`` on given inputs (X, G, H) of one dtype"""
+    X, G, H = xgh
+    n = X.shape[0]
     Xw, Gw, Hw = X.astype(wide), G.astype(wide), H.astype(wide)
     Xn, Hn = Xw.copy(), Hw.copy()
-    K, h = O.svgd_step(Xn, Gw, Hn, EPS, ALPHA, FUDGE, float(case.sign))
+    K, h = O.svgd_step(Xn, Gw, Hn, EPS, ALPHA, FUDGE, float(sign))
     f = lambda a: np.asarray(a, dtype=np.float64)
     disp = f(Xn - Xw)
     K, Xn, Hn, h = f(K), f(Xn), f(Hn), float(h)                     # the bars themselves need no more than f64
     absX, absG = np.abs(X.astype(np.float64)), np.abs(G.astype(np.float64))
-    S = (K @ absG + (K @ absX + absX * K.sum(axis=1)[:, None]) / (h * h)) / case.n
+    S = (K @ absG + (K @ absX + absX * K.sum(axis=1)[:, None]) / (h * h)) / n
     J = 1.0 / (FUDGE + np.sqrt(Hn))
     gt = np.abs(disp) / EPS / J
     return StepRef(X, G, H, K, h, disp, Hn, Xn, S, J, gt)

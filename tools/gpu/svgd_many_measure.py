@@ -6,11 +6,13 @@ with 129, 256, 512 and 1024 particles in f32 and f64:
   (c) the same step written as torch expressions on the device -- ``cdist``, sort-median, two matmuls and the tail -- which is
       what a user would write without these kernels;
   (d) one large-dim row: 256 x 1 000 003 in f32, (a) and (c);
-  (e) the bar units the kernels reach at the cases of tests/svgd_many_cases.py (the oracle runs on the host: a minute).
+  (e) the bar units the kernels reach at the cases of tests/svgd_many_cases.py (the oracle runs on the host: a minute);
+  (f) the cases of tests/svgd_many_exact_cases.py: whether the median of every lattice cloud is the oracle's bit for bit, and
+      the bar units at the small-n and translated cases (seconds; ``--exact-only`` runs nothing else).
 Device events on the stream around blocks of calls, medians of 9 blocks after a warm-up block, (a) and (c) alternating block
 by block. The record is profiles/svgd_many.txt.
 
-    python tools/gpu/svgd_many_measure.py [output file] [--no-units]
+    python tools/gpu/svgd_many_measure.py [output file] [--no-units] [--exact-only]
 """
 import math, os, sys, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -98,7 +100,8 @@ def entry_rows(n, d, ld, dt, calls):
     say("(c) torch restatement:             median %9.1f us (min %.1f, max %.1f)   (c)/(a) = %.2f" % (mc, lc, hc, mc / ma))
     assert torch.isfinite(x).all() and torch.isfinite(xt).all()
 
-for dt in (torch.float32, torch.float64):
+TIMINGS = "--exact-only" not in sys.argv
+for dt in (torch.float32, torch.float64) if TIMINGS else ():
     for n in (129, 256, 512, 1024):
         say("---- %d particles x %d (pitch %d), %s" % (n, P, PITCH, dt))
         entry_rows(n, P, PITCH, dt, 10)
@@ -110,11 +113,12 @@ for dt in (torch.float32, torch.float64):
                 "use_hip_graph=True" if graph else "eager             ", mb, lb, hb))
             del s
         torch.cuda.empty_cache()
-say("---- 256 particles x 1 000 003 (pitch 1 000 003), torch.float32")
-entry_rows(256, 1_000_003, 1_000_003, torch.float32, 3)
-torch.cuda.empty_cache()
+if TIMINGS:
+    say("---- 256 particles x 1 000 003 (pitch 1 000 003), torch.float32")
+    entry_rows(256, 1_000_003, 1_000_003, torch.float32, 3)
+    torch.cuda.empty_cache()
 
-if "--no-units" not in sys.argv:
+if TIMINGS and "--no-units" not in sys.argv:
     import svgd_many_cases as M
     import test_svgd_tile_walk_gpu as W
     say("---- units of the displacement bar at c = 1 (X, H) reached by the kernels; c = %.2f (f32), %.2f (f64)" % (M.C[M.F32], M.C[M.F64]))
@@ -135,4 +139,46 @@ if "--no-units" not in sys.argv:
             useK = float(np.max(np.abs(K.cpu().numpy() - K_ref) / (tol["atol"] + tol["rtol"] * np.abs(K_ref))))
             say("%-8s %4d x %-5d  sign +1: %6.3f %6.3f   sign -1: %6.3f %6.3f   K uses %.3f of its bar, h %.3f" % (
                 np.dtype(dtype).name, n, d, row[0], row[1], row[2], row[3], useK, abs(float(bw[1]) - h_ref) / h_ref / tol["rtol"]))
+if "--no-units" not in sys.argv:
+    import svgd_many_cases as M
+    import svgd_many_exact_cases as E
+    import test_svgd_tile_walk_gpu as W
+    to_dev = lambda a: torch.from_numpy(np.array(a)).to(dev)
+
+    def k_use(K, bw, K_ref, h_ref, dtype):
+        tol = M.TOL[dtype]
+        return (float(np.max(np.abs(K.cpu().numpy() - K_ref) / (tol["atol"] + tol["rtol"] * np.abs(K_ref)))),
+                abs(float(bw[1]) - h_ref) / h_ref / tol["rtol"])
+
+    def step_units(ref, n, d, dtype, sign):
+        x, g, h = (to_dev(a).reshape(-1) for a in (ref.X, ref.G, ref.H))
+        kernels.svgd_many_step(x, g, h, n, d, M.EPS, M.ALPHA, M.FUDGE, kernels.svgd_many_workspace(n, x), repulsion_sign=sign)
+        return list(W.bar_units(ref, dtype, x.cpu().numpy().reshape(n, d).astype(np.float64),
+                                h.cpu().numpy().reshape(n, d).astype(np.float64)))
+
+    say("---- lattice clouds: the median against the oracle in the case's own dtype, in keys (0: the same bits)")
+    for dtype in (M.F32, M.F64):
+        for family, n, d in E.LATTICE:
+            ref = E.exact_reference(family, n, d, dtype)
+            x = to_dev(ref.X)
+            K, _, bw = kernels.svgd_many_kernel(x.reshape(-1), n, d, kernels.svgd_many_workspace(n, x), kernel_gradients=False)
+            off = int(E.keys(bw.cpu().numpy()[:1])[0]) - int(E.keys(np.asarray(ref.med, dtype).reshape(1))[0])
+            f = E.select_facts(ref.D)
+            say("%-8s %-8s %4d x %-4d median %-22r %+d keys from the oracle's; %3d distinct keys, count_le - mid = %-6d  "
+                "K uses %.3f of its bar, h %.3f" % ((np.dtype(dtype).name, family, n, d, float(bw[0]), off, f.distinct,
+                                                     f.count_le - f.mid) + k_use(K, bw, ref.K, ref.h, dtype)))
+    say("---- 2 .. 127 particles and translated clouds: units of the displacement bar at c = 1 (X, H)")
+    for dtype in (M.F32, M.F64):
+        for kind, cases in (("small", E.SMALL), ("translated", E.TRANSLATED)):
+            for n, d in cases:
+                row = []
+                for sign in (1, -1):
+                    ref = (M.step_reference(M.Case(n, d, dtype, sign)) if kind == "small"
+                           else E.translated_step_reference(n, d, dtype, sign))
+                    row += step_units(ref, n, d, dtype, sign)
+                Xk, K_ref, _, h_ref, _ = (M.kernel_reference if kind == "small" else E.translated_kernel_reference)(n, d, dtype)
+                xk = to_dev(Xk)
+                K, _, bw = kernels.svgd_many_kernel(xk.reshape(-1), n, d, kernels.svgd_many_workspace(n, xk), kernel_gradients=False)
+                say("%-8s %-10s %4d x %-4d sign +1: %6.3f %6.3f   sign -1: %6.3f %6.3f   K uses %.3f of its bar, h %.3f" % (
+                    (np.dtype(dtype).name, kind, n, d, row[0], row[1], row[2], row[3]) + k_use(K, bw, K_ref, h_ref, dtype)))
 say("done")
