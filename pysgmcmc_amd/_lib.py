@@ -55,6 +55,7 @@ PREDICT_GRAD_ABI_VERSION = 1  # SGMCMC_PREDICT_GRAD_ABI_VERSION of include/sgmcm
 PARTICLES_ABI_VERSION = 1     # SGMCMC_PARTICLES_ABI_VERSION of include/sgmcmc_hip_particles.h (the particle-gradient add-on)
 SVGD_MANY_ABI_VERSION = 1     # SGMCMC_SVGD_MANY_ABI_VERSION of include/sgmcmc_hip_svgd_many.h (SVGD with up to 1024 particles)
 KSD_ABI_VERSION = 1           # SGMCMC_KSD_ABI_VERSION of include/sgmcmc_hip_ksd.h (the kernel Stein discrepancy, K16)
+THIN_ABI_VERSION = 1          # SGMCMC_THIN_ABI_VERSION of include/sgmcmc_hip_thin.h (Stein thinning, K17)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
@@ -300,6 +301,15 @@ def _declare(lib):
         f = getattr(lib, "sgmcmc_ksd_" + sfx)
         f.argtypes = [_vp, _sz, _vp, _sz, _sz, _sz, _ci] + [ctypes.c_double] * 3 + [_vp, _vp, _sz, _vp, _vp, _vp]
         f.restype = _ci
+    # include/sgmcmc_hip_thin.h: matrix, ld_m, n, m, batch, batch_stride, flags, indices_out, path_out, stream
+    lib.sgmcmc_stein_thin_abi_version.restype = _ci
+    lib.sgmcmc_stein_thin_max_samples.restype = _ci
+    lib.sgmcmc_stein_thin_plan.argtypes = [_sz, _sz, _sz, ctypes.POINTER(_ci), _ci]
+    lib.sgmcmc_stein_thin_plan.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_stein_thin_" + sfx)
+        f.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, _ci, _vp, _vp, _vp]
+        f.restype = _ci
 
 
 def lib():
@@ -338,6 +348,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: many-particle SVGD add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_ksd_abi_version() != KSD_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: kernel Stein discrepancy add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_stein_thin_abi_version() != THIN_ABI_VERSION:
+        raise SgmcmcLibraryError("pysgmcmc_amd: Stein thinning add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

@@ -16,6 +16,11 @@ and ``V = (1 / n^2) sum_ij k_p`` (the squared discrepancy of the empirical measu
   ``stein_kernel_matrix``        the host statement of K16's arithmetic contract in numpy; the precision of the three
                                  families of sums over the columns is an argument
   ``stein_sums``                 the contract's order of the row sums, the total and the trace
+  ``stein_thinning``             greedy Stein thinning (Riabiz et al., *Optimal thinning of MCMC output*): ``m`` of the rows,
+                                 picked one at a time to minimise the discrepancy of the picked set. Device inputs: one call
+                                 of K16 for the matrix, one of K17 (``kernels.stein_thin``, ``include/sgmcmc_hip_thin.h``)
+                                 for the picks; host inputs: the two host statements
+  ``stein_thinning_indices``     the host statement of K17's arithmetic contract in numpy
 
 Base kernels: ``"imq"``, ``phi = (c^2 + r2)^beta`` with ``c > 0`` and ``-1 < beta < 0`` (the default ``c = 1``,
 ``beta = -1/2``: the kernel Gorham & Mackey show to detect non-convergence in more than two dimensions), and ``"rbf"``,
@@ -30,7 +35,8 @@ import torch
 from pysgmcmc_amd import kernels
 from pysgmcmc_amd.diagnostics.device_trace import DeviceTrace
 
-__all__ = ["SteinDiscrepancy", "kernel_stein_discrepancy", "stein_kernel_matrix", "stein_sums", "MAX_SAMPLES"]
+__all__ = ["SteinDiscrepancy", "kernel_stein_discrepancy", "stein_kernel_matrix", "stein_sums", "MAX_SAMPLES",
+           "SteinThinning", "stein_thinning", "stein_thinning_indices"]
 
 MAX_SAMPLES = 4096            # sgmcmc_ksd_max_samples()
 _LANES = 256
@@ -40,6 +46,11 @@ SteinDiscrepancy = collections.namedtuple("SteinDiscrepancy", "ksd v_statistic u
 SteinDiscrepancy.__doc__ = """``ksd = sqrt(max(V, 0))``, the V- and the U-statistic, the ``n`` row sums of the Stein kernel
 matrix, the matrix itself (``return_matrix=True``, else None) and ``thinning``: every ``thinning``-th row of the trace was
 used (1 unless an entry above thinned a trace longer than 4096 rows)."""
+
+SteinThinning = collections.namedtuple("SteinThinning", "indices ksd_path v_path discrepancy")
+SteinThinning.__doc__ = """``indices``: the ``m`` picked rows in the order they were picked (int32; ``(chains, m)`` and local to
+the chain with ``per_chain=True``); ``v_path[t - 1]``: the V-statistic of the first ``t`` picks, ``ksd_path`` its clamped
+square root; ``discrepancy``: the ``SteinDiscrepancy`` of the whole set, its ``matrix`` the one the picks were made from."""
 
 
 def _check_kernel(kernel, c, beta, bandwidth):
@@ -235,3 +246,94 @@ def kernel_stein_discrepancy(samples, scores, kernel="imq", c=1.0, beta=-0.5, ba
     if as_torch:
         out = tuple(None if o is None else torch.as_tensor(o, dtype=torch.float64) for o in out)
     return SteinDiscrepancy(*out)
+
+
+def stein_thinning_indices(matrix, m, distinct=False):
+    """Greedy Stein thinning of the ``(n, n)`` Stein kernel matrix ``matrix``: ``(indices, path)``, ``m`` int32 row numbers in
+    the order they are picked and the float64 V-statistic of the first ``t`` picks. The host statement of the arithmetic
+    contract of ``include/sgmcmc_hip_thin.h``, in double, every written operation rounded once:
+
+        h_j = 0.5 K_jj,  acc_j = 0,  S = 0;  for t = 1 .. m:
+            obj_j = acc_j + h_j;   j* = the candidate with the smallest obj_j, among equal values the smallest j
+            S = S + 2 obj_j*;   indices[t - 1] = j*;   path[t - 1] = S / (t t);   acc_j = acc_j + K[j*][j]  (row j*)
+
+    Every row is a candidate at every step; with ``distinct`` a picked row is not a candidate again (``m <= n``)."""
+    K = np.asarray(matrix)
+    if K.ndim != 2 or K.shape[0] != K.shape[1] or K.shape[0] < 2:
+        raise ValueError("stein_thinning_indices: matrix must be (n, n) with n >= 2, got %s" % (tuple(K.shape),))
+    n, m = K.shape[0], int(m)
+    if m < 1:
+        raise ValueError("stein_thinning_indices: m must be at least 1, got %d" % m)
+    if distinct and m > n:
+        raise ValueError("stein_thinning_indices: distinct picks need m <= n, got m = %d, n = %d" % (m, n))
+    h = 0.5 * np.diag(K).astype(np.float64)
+    acc = np.zeros(n)
+    free = np.ones(n, dtype=bool)
+    indices, path = np.empty(m, dtype=np.int32), np.empty(m)
+    S = 0.0
+    for t in range(1, m + 1):
+        obj = acc + h
+        if distinct:
+            cand = np.flatnonzero(free)
+            j = int(cand[np.argmin(obj[cand])])                  # argmin: the first of equal values
+            free[j] = False
+        else:
+            j = int(np.argmin(obj))
+        S = S + 2.0 * float(obj[j])
+        indices[t - 1], path[t - 1] = j, S / (float(t) * float(t))
+        acc = acc + K[j].astype(np.float64)
+    return indices, path
+
+
+def _as_chains(a, what):
+    if isinstance(a, DeviceTrace):
+        a = a.values()
+    if not torch.is_tensor(a):
+        a = np.asarray(a)
+    if a.ndim != 3:
+        raise ValueError("stein_thinning: per_chain=True needs %s as (chains, n, d), got %s" % (what, tuple(a.shape)))
+    return int(a.shape[0]), int(a.shape[1])
+
+
+def stein_thinning(samples, scores, m, kernel="imq", c=1.0, beta=-0.5, bandwidth=None, distinct=False, per_chain=False,
+                   workspace=None):
+    """Greedy Stein thinning of ``samples`` with the scores ``scores = grad log p(samples)``: a ``SteinThinning`` of the ``m``
+    rows that, picked one at a time, keep the kernel Stein discrepancy of the picked set smallest -- the small ensemble to
+    predict with, instead of every k-th row.
+
+    ``samples`` / ``scores``, the kernel arguments and ``workspace`` are those of ``kernel_stein_discrepancy``: ``(n, d)`` or
+    ``(chains, n, d)`` or a ``DeviceTrace``, 2 .. 4096 rows in all, else ``ValueError``. ``per_chain=False`` pools the rows:
+    ``indices`` is ``(m,)`` into the flattened rows. ``per_chain=True`` needs the three-dimensional form and thins each chain
+    on its own diagonal block of the one pooled matrix: ``indices`` and the paths are ``(chains, m)``, the indices local to
+    the chain. ``distinct``: no row is picked twice (``m`` at most the rows of a problem); without it a row may repeat, which
+    weights it.
+
+    Device tensors: one K16 call with ``return_matrix=True``, then one K17 call (``kernels.stein_thin``); every field is a
+    device tensor and nothing waits for the host. CPU tensors and numpy arrays: ``stein_kernel_matrix`` and
+    ``stein_thinning_indices`` in double. The particles of an SVGD sampler go through unchanged:
+    ``stein_thinning(sampler.particles, models.bnn_posterior_scores(sampler.particles, ...), m)``."""
+    m = int(m)
+    if m < 1:
+        raise ValueError("stein_thinning: m must be at least 1, got %d" % m)
+    chains, rows = (_as_chains(samples, "samples") if per_chain else (1, None))
+    if per_chain and _as_chains(scores, "scores") != (chains, rows):
+        raise ValueError("stein_thinning: samples and scores differ in shape")
+    disc = kernel_stein_discrepancy(samples, scores, kernel, c, beta, bandwidth, return_matrix=True, workspace=workspace)
+    K = disc.matrix
+    n = int(K.shape[0]) if rows is None else rows
+    if n < 2:
+        raise ValueError("stein_thinning: a chain needs at least 2 rows, got %d" % n)
+    if distinct and m > n:
+        raise ValueError("stein_thinning: distinct picks need m <= %d rows, got m = %d" % (n, m))
+    if torch.is_tensor(K) and K.is_cuda:
+        idx, v = kernels.stein_thin(K, m, distinct=distinct, n=n, batch=chains, batch_stride=n * int(K.stride(0)) + n)
+        if per_chain:
+            idx, v = idx.view(chains, m), v.view(chains, m)
+        return SteinThinning(idx, torch.sqrt(torch.clamp(v, min=0.0)), v, disc)
+    Kn = K.numpy() if torch.is_tensor(K) else K
+    parts = [stein_thinning_indices(Kn[p * n:(p + 1) * n, p * n:(p + 1) * n], m, distinct) for p in range(chains)]
+    idx, v = (np.stack([p[k] for p in parts]) if per_chain else parts[0][k] for k in (0, 1))
+    out = (idx, np.sqrt(np.maximum(v, 0.0)), v)
+    if torch.is_tensor(K):
+        out = tuple(torch.as_tensor(o) for o in out)
+    return SteinThinning(*out, disc)

@@ -24,6 +24,7 @@ __all__ = [
     "bnn_predict_grad", "bnn_predict_grad_row_tile", "bnn_particles_cost_grad", "bnn_particles_lds_bytes",
     "svgd_many_max_particles", "svgd_many_workspace", "svgd_many_step", "svgd_many_kernel", "svgd_many_plan",
     "ksd_max_samples", "ksd_workspace", "ksd_plan", "ksd",
+    "stein_thin_max_samples", "stein_thin_plan", "stein_thin",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -1369,3 +1370,62 @@ def ksd(samples, scores, workspace, kind="imq", c=1.0, beta=-0.5, h2=None, matri
                _ptr(row_sums), _ptr(stats), _stream(samples))
     check(rc, "sgmcmc_ksd")
     return stats
+
+
+# ---- K17: greedy Stein thinning from a Stein kernel matrix (include/sgmcmc_hip_thin.h, csrc/sgmcmc_stein_thin.hip) ----
+SteinThinLaunch = collections.namedtuple("SteinThinLaunch", "block columns_per_thread grid waves")
+STEIN_THIN_DISTINCT = 1
+
+
+def stein_thin_max_samples():
+    return int(lib().sgmcmc_stein_thin_max_samples())
+
+
+def stein_thin_plan(n, m, batch=1):
+    """The launch of one ``stein_thin`` call: ``SteinThinLaunch(block, columns_per_thread, grid, waves)`` (host arithmetic)."""
+    out = (ctypes.c_int * 4)()
+    rc = int(lib().sgmcmc_stein_thin_plan(int(n), int(m), int(batch), out, 4))
+    check(0 if rc > 0 else rc, "sgmcmc_stein_thin_plan")
+    return SteinThinLaunch(*out)
+
+
+def stein_thin(matrix, m, indices=None, path=None, distinct=False, n=None, batch=1, batch_stride=0):
+    """K17 (``sgmcmc_stein_thin_*``): greedy Stein thinning, ``m`` picks from each of ``batch`` blocks of ``n x n`` elements of
+    the device matrix ``matrix`` (two-dimensional, dense rows, any row pitch; what ``ksd`` writes as ``matrix``), in one launch
+    on the current stream without host synchronisation. Block ``p`` starts ``p * batch_stride`` elements behind the first
+    element, ``batch_stride = n * matrix.stride(0) + n`` walks diagonal blocks; ``n`` defaults to the number of rows (one block:
+    the whole matrix). ``distinct``: a picked row is not picked again (``m <= n``). ``indices``: ``batch * m`` int32,
+    ``path``: ``batch * m`` float64 (the V-statistic of the first ``t`` picks), both contiguous, allocated when None as
+    ``(m,)``, or ``(batch, m)`` when ``batch > 1``. Returns ``(indices, path)``; the indices are local to their block."""
+    what = "stein_thin"
+    f = getattr(lib(), "sgmcmc_stein_thin_" + _sfx(matrix))
+    if matrix.dim() != 2:
+        raise ValueError("%s: matrix must be two-dimensional" % what)
+    rows, cols = int(matrix.shape[0]), int(matrix.shape[1])
+    if (cols > 1 and matrix.stride(1) != 1) or (rows > 1 and matrix.stride(0) < cols):
+        raise ValueError("%s: matrix must have dense rows that do not overlap" % what)
+    n = rows if n is None else int(n)
+    m, batch, batch_stride = int(m), int(batch), int(batch_stride)
+    ld = int(matrix.stride(0)) if rows > 1 else cols
+    if n < 1 or m < 1 or batch < 1 or batch_stride < 0:
+        raise ValueError("%s: n, m and batch must be positive and batch_stride non-negative" % what)
+    # the last block, like every block before it, must lie inside the matrix
+    r0, c0 = divmod((batch - 1) * batch_stride, max(ld, 1))
+    if r0 + n > rows or c0 + n > cols:
+        raise ValueError("%s: block %d of %d x %d elements at offset %d does not lie inside the %d x %d matrix"
+                         % (what, batch - 1, n, n, (batch - 1) * batch_stride, rows, cols))
+    shape = (m,) if batch == 1 else (batch, m)
+    for t, name, dt in ((indices, "indices", torch.int32), (path, "path", torch.float64)):
+        if t is not None and (t.dtype != dt or t.device != matrix.device or t.numel() != batch * m or not t.is_contiguous()):
+            raise ValueError("%s: %s must be %d contiguous %s elements on %s" % (what, name, batch * m, dt, matrix.device))
+    if not matrix.is_cuda:
+        _ptr(matrix)                     # raises the no-CPU-path error
+    if indices is None:
+        indices = torch.empty(shape, dtype=torch.int32, device=matrix.device)
+    if path is None:
+        path = torch.empty(shape, dtype=torch.float64, device=matrix.device)
+    with torch.cuda.device(matrix.device):
+        rc = f(matrix.data_ptr(), ld, n, m, batch, batch_stride, STEIN_THIN_DISTINCT if distinct else 0, _ptr(indices),
+               _ptr(path), _stream(matrix))
+    check(rc, "sgmcmc_stein_thin")
+    return indices, path

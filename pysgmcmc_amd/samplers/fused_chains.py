@@ -194,6 +194,41 @@ class FusedBNNChains(object):
         out = kernel_stein_discrepancy(x, self.posterior_scores(x), **kw)
         return out._replace(thinning=k)
 
+    def thin(self, trace, m, per_chain=False, **kw):
+        """A small ensemble from ``trace`` (what :meth:`collect` returns, or an ``(n, P)`` matrix) by greedy Stein thinning
+        instead of every k-th row: the scores from :meth:`posterior_scores`, then
+        ``diagnostics.stein_thinning(samples, scores, m, per_chain=per_chain, **kw)`` (kernels K16 and K17), then the picked
+        rows gathered on the device. Returns ``(ensemble, result)``: ``ensemble`` is an ``(m, P)`` matrix, or
+        ``(chains * m, P)`` with ``per_chain=True`` (``m`` rows of every chain, picked on that chain alone), which
+        :meth:`predict`, :meth:`score` and :meth:`predictive_gradients` accept as they accept a trace; ``result`` is the
+        ``diagnostics.SteinThinning`` of device tensors. A trace of more than 4096 rows in all is first strided evenly as
+        :meth:`stein_discrepancy` does: ``result.indices`` still index the rows of ``trace`` itself (the flattened rows, or
+        the rows of the chain with ``per_chain=True``) and ``result.discrepancy.thinning`` reports the stride. Nothing waits
+        for the host."""
+        from pysgmcmc_amd.diagnostics.stein import MAX_SAMPLES, stein_thinning
+        if not torch.is_tensor(trace):
+            trace = trace.values()
+        x = trace if trace.dim() == 3 else trace.unsqueeze(0)
+        chains, n, P = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+        if chains > MAX_SAMPLES:
+            raise ValueError("FusedBNNChains.thin: %d chains, the limit is %d samples in all" % (chains, MAX_SAMPLES))
+        k = 1
+        while chains * len(range(0, n, k)) > MAX_SAMPLES:
+            k += 1
+        xs = (x[:, ::k] if k > 1 else x).reshape(-1, P)
+        kept = int(xs.shape[0]) // chains
+        scores = self.posterior_scores(xs)
+        result = stein_thinning(xs.view(chains, kept, P), scores.view(chains, kept, P), m, per_chain=per_chain, **kw)
+        idx = result.indices.long()
+        if per_chain:
+            local = idx * k                                                   # (chains, m), rows of the chain
+            flat = (local + n * torch.arange(chains, device=idx.device).unsqueeze(1)).reshape(-1)
+        else:
+            flat = local = (idx // kept) * n + (idx % kept) * k               # (m,), rows of the flattened trace
+        ensemble = x.reshape(-1, P).index_select(0, flat)
+        result = result._replace(indices=local.to(torch.int32), discrepancy=result.discrepancy._replace(thinning=k))
+        return ensemble, result
+
     @classmethod
     def for_dataset(cls, X, y, n_chains, hidden=(50, 50, 50), batch_size=20, seed=0, dtype=torch.float32,
                     device="cuda:0", stepsize=0.01, burn_in_steps=1000, mdecay=0.05, init_seed=None):

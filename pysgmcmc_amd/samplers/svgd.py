@@ -48,6 +48,10 @@ class SVGDSampler(MCMCSampler):
 
     ``next(sampler)`` returns ``(particles, costs)``: the list of updated particles and the
     vector of the ``n`` costs at the particles before the step.
+
+    ``sampler.particles`` is the ``(n, d)`` particle matrix on the device. With the scores of its rows
+    (``models.bnn_posterior_scores`` for the small BNN) it goes as it is to ``diagnostics.kernel_stein_discrepancy`` and to
+    ``diagnostics.stein_thinning``, which picks the few particles to predict with.
     """
 
     _STATE_ROWS = ("historical_grad",)
