@@ -56,10 +56,13 @@ PARTICLES_ABI_VERSION = 1     # SGMCMC_PARTICLES_ABI_VERSION of include/sgmcmc_h
 SVGD_MANY_ABI_VERSION = 1     # SGMCMC_SVGD_MANY_ABI_VERSION of include/sgmcmc_hip_svgd_many.h (SVGD with up to 1024 particles)
 KSD_ABI_VERSION = 1           # SGMCMC_KSD_ABI_VERSION of include/sgmcmc_hip_ksd.h (the kernel Stein discrepancy, K16)
 THIN_ABI_VERSION = 1          # SGMCMC_THIN_ABI_VERSION of include/sgmcmc_hip_thin.h (Stein thinning, K17)
+RANK_ABI_VERSION = 1          # SGMCMC_RANK_ABI_VERSION of include/sgmcmc_hip_rank.h (rank normalisation, K18)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
 CHAINS_MAX_CHAINS = 4096
+RANK_MAX_CHAINS = 2048        # SGMCMC_RANK_MAX_CHAINS: the 2 m split chains must fit K12
+RANK_MAX_POOLED = 8192        # SGMCMC_RANK_MAX_POOLED: pooled draws of one parameter, N = 2 m (n // 2)
 SCORE_MAX_CHAINS = 64
 PREDICT_GRAD_MAX_CHAINS = 64
 
@@ -310,6 +313,13 @@ def _declare(lib):
         f = getattr(lib, "sgmcmc_stein_thin_" + sfx)
         f.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, _ci, _vp, _vp, _vp]
         f.restype = _ci
+    # include/sgmcmc_hip_rank.h: trace, m, n, P, ld, chain_stride, z, z_folded, tail_lo, tail_hi, ld_out, chain_stride_out, stream
+    lib.sgmcmc_rank_abi_version.restype = _ci
+    lib.sgmcmc_rank_max_pooled.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_rank_normalize_" + sfx)
+        f.argtypes = [_vp, _ci, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _vp]
+        f.restype = _ci
 
 
 def lib():
@@ -350,6 +360,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: kernel Stein discrepancy add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_stein_thin_abi_version() != THIN_ABI_VERSION:
         raise SgmcmcLibraryError("pysgmcmc_amd: Stein thinning add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_rank_abi_version() != RANK_ABI_VERSION or handle.sgmcmc_rank_max_pooled() != RANK_MAX_POOLED:
+        raise SgmcmcLibraryError("pysgmcmc_amd: rank normalisation add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

@@ -13,6 +13,8 @@ its estimator for ONE scalar (an FFT and a host read per call). Here the trace n
   ``chain_diagnostics_all``       one launch of K12 (``kernels.chain_diag``) -> float64 R-hat AND int64 ESS of all P
                                   parameters from up to 4096 chains (K10 stops at 64); ``gelman_rubin_all`` is its
                                   R-hat-only launch
+  ``rank_diagnostics_all``        one launch of K18 (``kernels.rank_normalize``) and two of K12 -> the rank-normalised split
+                                  R-hat and the bulk and tail ESS of all P parameters
   ``effective_sample_sizes_of``   the reference's ``{name: array shaped like the parameter}`` cut from that vector
 
 Scope: chains that share a device (``ConcurrentChains``, sequential chains as in ``multitrace``, the stacked state of
@@ -24,7 +26,8 @@ import torch
 
 from pysgmcmc_amd import kernels
 
-__all__ = ["DeviceTrace", "effective_n_all", "effective_sample_sizes_of", "chain_diagnostics_all", "gelman_rubin_all"]
+__all__ = ["DeviceTrace", "effective_n_all", "effective_sample_sizes_of", "chain_diagnostics_all", "gelman_rubin_all",
+           "rank_diagnostics_all"]
 
 
 class DeviceTrace(object):
@@ -239,6 +242,59 @@ def chain_diagnostics_all(traces, details=False):
     stop = torch.empty(P, dtype=torch.int32, device=dev) if details else None
     kernels.chain_diag(x, rhat, ess, raw, stop)
     return (rhat, ess, raw, stop) if details else (rhat, ess)
+
+
+def rank_diagnostics_all(traces, details=False):
+    """Rank-normalised split R-hat, bulk ESS and tail ESS of each of the P parameters (Vehtari, Gelman, Simpson, Carpenter,
+    Buerkner 2021): ``(rhat_rank, ess_bulk, ess_tail)``, float64 / int64 / int64 ``(P,)`` device tensors. Where the classic
+    R-hat of :func:`chain_diagnostics_all` compares the chains' means and needs a finite variance, this one also sees chains
+    that agree in location and differ in scale, and heavy tails do not break it.
+
+    ``traces``: what :func:`chain_diagnostics_all` accepts, with at most 2048 chains of at least 4 samples and at most
+    ``kernels.rank_max_pooled()`` pooled draws ``N = 2 m (n // 2)`` per parameter. Every chain is split in two. ONE launch
+    of K18 (``kernels.rank_normalize``) writes, into one ``(2 m, n // 2, 4 P)`` buffer, the normal scores ``z`` of the pooled
+    ranks (average ranks over ties), the scores ``z_folded`` of ``|x - median|`` and the indicators ``tail_lo`` / ``tail_hi``
+    of the pooled 5 % and 95 % order statistics; K12 (``kernels.chain_diag``) then reads column blocks of that buffer: an
+    R-hat-only launch over ``[z_folded | z]`` and a full one over ``[z | tail_lo | tail_hi]``.
+
+        rhat_rank = max(rhat(z), rhat(z_folded))     ess_bulk = ess(z)     ess_tail = min(ess(tail_lo), ess(tail_hi))
+
+    with the maximum and the minimum taken on the device (a NaN R-hat on either side gives NaN). With ``details=True`` the
+    result is the ``rank.RankDiagnostics`` tuple of device tensors: those three, then ``rhat_bulk``, ``rhat_folded``,
+    ``ess_tail_lo``, ``ess_tail_hi`` and the untruncated ``raw_bulk``, ``raw_tail_lo``, ``raw_tail_hi``. A parameter with a
+    NaN or an infinite sample, or a constant one, is degenerate: R-hat NaN, ESS 0. Nothing here waits for the host.
+
+    Two deviations from ArviZ. (1) The ESS estimator is K12's variogram rule (that of ``effective_n``) applied to the
+    transformed split chains, not Geyer's initial monotone sequence; the R-hat formula is the same. (2) The tail indicators
+    are taken against order statistics of the POOLED SPLIT draws, so for odd ``n`` the middle draw of every chain, which the
+    split drops, does not enter the quantiles either."""
+    from pysgmcmc_amd.diagnostics.rank import RankDiagnostics
+    who = "rank_diagnostics_all"
+    x = _stacked_trace(traces, who)
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    m, n, P = (int(v) for v in x.shape)
+    if m > 2048:
+        raise ValueError("%s: at most 2048 chains, got %d" % (who, m))
+    if n < 4:
+        raise ValueError("%s: needs at least 4 samples per chain, got %d" % (who, n))
+    dev, half = x.device, n // 2
+    buf = torch.empty(2 * m, half, 4 * P, dtype=torch.float64, device=dev)
+    zf, z, lo, hi = (buf[:, :, k * P:(k + 1) * P] for k in range(4))
+    kernels.rank_normalize(x, z=z, z_folded=zf, tail_lo=lo, tail_hi=hi)
+    rhat2 = torch.empty(2 * P, dtype=torch.float64, device=dev)
+    ess3 = torch.empty(3 * P, dtype=torch.int64, device=dev)
+    raw3 = torch.empty(3 * P, dtype=torch.float64, device=dev) if details else None
+    if P:
+        kernels.chain_diag(buf[:, :, :2 * P], rhat=rhat2)
+        kernels.chain_diag(buf[:, :, P:], ess=ess3, raw=raw3)
+    rhat_f, rhat_z = rhat2[:P], rhat2[P:]
+    ess_bulk, ess_lo, ess_hi = ess3[:P], ess3[P:2 * P], ess3[2 * P:]
+    rhat = torch.maximum(rhat_z, rhat_f)
+    ess_tail = torch.minimum(ess_lo, ess_hi)
+    if not details:
+        return rhat, ess_bulk, ess_tail
+    return RankDiagnostics(rhat, ess_bulk, ess_tail, rhat_z, rhat_f, ess_lo, ess_hi, raw3[:P], raw3[P:2 * P], raw3[2 * P:])
 
 
 def effective_sample_sizes_of(samplers_or_traces, param_shapes=None, names=None):

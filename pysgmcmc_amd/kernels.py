@@ -13,7 +13,7 @@ import ctypes
 
 import torch
 
-from pysgmcmc_amd._lib import SgmcmcLibraryError, check, lib
+from pysgmcmc_amd._lib import RANK_MAX_CHAINS, RANK_MAX_POOLED, SgmcmcLibraryError, check, lib
 
 __all__ = [
     "sghmc_step", "sgld_step", "rsghmc_step", "update_step", "philox_normal", "philox_bits",
@@ -25,6 +25,7 @@ __all__ = [
     "svgd_many_max_particles", "svgd_many_workspace", "svgd_many_step", "svgd_many_kernel", "svgd_many_plan",
     "ksd_max_samples", "ksd_workspace", "ksd_plan", "ksd",
     "stein_thin_max_samples", "stein_thin_plan", "stein_thin",
+    "rank_normalize", "rank_max_pooled",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -1429,3 +1430,76 @@ def stein_thin(matrix, m, indices=None, path=None, distinct=False, n=None, batch
                _ptr(path), _stream(matrix))
     check(rc, "sgmcmc_stein_thin")
     return indices, path
+
+
+def rank_max_pooled():
+    """The largest pooled count ``N = 2 m (n // 2)`` of one ``rank_normalize`` call (``SGMCMC_RANK_MAX_POOLED``)."""
+    return RANK_MAX_POOLED
+
+
+def rank_normalize(trace, z=None, z_folded=None, tail_lo=None, tail_hi=None):
+    """K18 (``include/sgmcmc_hip_rank.h``): the rank normalisation of every parameter of ONE strided trace, in one launch on
+    the current stream: the draws of the ``2 m`` split chains pooled, ranked with average ranks over ties and mapped through
+    the inverse normal CDF (``z``), the same for ``|x - median|`` (``z_folded``), and the indicators of the lower and upper
+    5 % tails (``tail_lo``, ``tail_hi``). K12 (``chain_diag``) turns them into rank-normalised R-hat, bulk and tail ESS.
+
+    ``trace``: an ``(m, n, P)`` device tensor, or ``(n, P)`` for a single chain, float32 or float64, dense rows;
+    ``ld = stride(1)``, ``chain_stride = stride(0)`` as for ``chain_diag``. ``n >= 4``, ``m <= 2048`` and
+    ``2 m (n // 2) <= rank_max_pooled()``. The outputs, at least one, are float64 ``(2 m, n // 2, P)`` tensors on the trace's
+    device with dense rows and COMMON strides (column blocks of one ``(2 m, n // 2, 4 P)`` buffer, say). Shapes and dtypes
+    are checked before a device is touched. Returns ``(z, z_folded, tail_lo, tail_hi)`` as passed."""
+    what = "rank_normalize"
+    if not torch.is_tensor(trace):
+        raise TypeError("%s: trace must be an (m, n, P) or (n, P) device tensor" % what)
+    if trace.dim() == 2:
+        trace = trace.unsqueeze(0)
+    if trace.dim() != 3:
+        raise ValueError("%s: trace must be (m, n, P) or (n, P), got %s" % (what, tuple(trace.shape)))
+    sfx = _sfx(trace)
+    m, n, P = (int(v) for v in trace.shape)
+    if m < 1 or m > RANK_MAX_CHAINS:
+        raise ValueError("%s: m = %d chains, must be 1 .. %d" % (what, m, RANK_MAX_CHAINS))
+    if n < 4:
+        raise ValueError("%s: needs at least 4 samples per chain, got n = %d" % (what, n))
+    half = n // 2
+    if 2 * m * half > RANK_MAX_POOLED:
+        raise ValueError("%s: N = 2 * %d * %d = %d pooled draws, at most %d" % (what, m, half, 2 * m * half, RANK_MAX_POOLED))
+    if P > 1 and trace.stride(2) != 1:
+        raise ValueError("%s: rows must be dense (stride 1 along the parameters)" % what)
+    ld = int(trace.stride(1))
+    chain_stride = int(trace.stride(0)) if m > 1 else (n - 1) * ld + P
+    if ld < 0 or chain_stride < 0:
+        raise ValueError("%s: negative strides are not supported" % what)
+    outs = ((z, "z"), (z_folded, "z_folded"), (tail_lo, "tail_lo"), (tail_hi, "tail_hi"))
+    if all(out is None for out, _ in outs):
+        raise ValueError("%s: at least one of z, z_folded, tail_lo and tail_hi is required" % what)
+    ld_out = chain_stride_out = None
+    for out, name in outs:
+        if out is None:
+            continue
+        if not torch.is_tensor(out) or out.dtype != torch.float64:
+            raise TypeError("%s: %s must be a float64 tensor" % (what, name))
+        if tuple(out.shape) != (2 * m, half, P):
+            raise ValueError("%s: %s must be of shape (2 m, n // 2, P) = %s, got %s" % (what, name, (2 * m, half, P),
+                                                                                        tuple(out.shape)))
+        if out.device != trace.device:
+            raise ValueError("%s: %s must live on %s" % (what, name, trace.device))
+        if P > 1 and out.stride(2) != 1:
+            raise ValueError("%s: the rows of %s must be dense" % (what, name))
+        strides = (int(out.stride(1)) if half > 1 else P, int(out.stride(0)))
+        if ld_out is None:
+            ld_out, chain_stride_out = strides
+        elif strides != (ld_out, chain_stride_out):
+            raise ValueError("%s: the outputs must share their strides, %s has %s against %s" % (
+                what, name, strides, (ld_out, chain_stride_out)))
+    if ld_out < P or chain_stride_out < (half - 1) * ld_out + P:
+        raise ValueError("%s: the outputs' rows or chains overlap (strides %s)" % (what, (chain_stride_out, ld_out)))
+    if not trace.is_cuda:
+        raise SgmcmcLibraryError("pysgmcmc_amd: trace lives on %s; the rank normalisation runs only as a HIP kernel on an "
+                                 "AMD GPU (no CPU fallback)." % trace.device)
+    f = getattr(lib(), "sgmcmc_rank_normalize_" + sfx)
+    with torch.cuda.device(trace.device):
+        rc = f(trace.data_ptr(), m, n, P, ld, chain_stride, *[None if out is None else out.data_ptr() for out, _ in outs],
+               ld_out, chain_stride_out, _stream(trace))
+    check(rc, "sgmcmc_rank_normalize")
+    return z, z_folded, tail_lo, tail_hi

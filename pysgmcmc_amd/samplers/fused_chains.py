@@ -117,10 +117,17 @@ class FusedBNNChains(object):
             self.steps(n_samples * every, trace=out, keep_every=every)
         return out
 
-    def diagnose(self, trace, details=False):
+    def diagnose(self, trace, details=False, rank_normalized=False):
         """R-hat and effective sample size of every parameter over all the chains of ``trace`` (what :meth:`collect`
         returns) in one device launch: ``diagnostics.chain_diagnostics_all(trace, details)`` -> ``(rhat, ess)``, or
-        ``(rhat, ess, raw, stop_lag)`` with ``details=True``. Nothing waits for the host."""
+        ``(rhat, ess, raw, stop_lag)`` with ``details=True``. Nothing waits for the host.
+
+        ``rank_normalized=True``: the rank-normalised split R-hat and the bulk and tail effective sample sizes instead,
+        ``diagnostics.rank_diagnostics_all(trace, details)`` -> ``(rhat_rank, ess_bulk, ess_tail)``: they also see chains
+        that agree in location and differ in scale, and do not need a finite variance."""
+        if rank_normalized:
+            from pysgmcmc_amd.diagnostics.device_trace import rank_diagnostics_all
+            return rank_diagnostics_all(trace, details)
         from pysgmcmc_amd.diagnostics.device_trace import chain_diagnostics_all
         return chain_diagnostics_all(trace, details)
 
