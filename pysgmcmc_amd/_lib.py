@@ -57,12 +57,14 @@ SVGD_MANY_ABI_VERSION = 1     # SGMCMC_SVGD_MANY_ABI_VERSION of include/sgmcmc_h
 KSD_ABI_VERSION = 1           # SGMCMC_KSD_ABI_VERSION of include/sgmcmc_hip_ksd.h (the kernel Stein discrepancy, K16)
 THIN_ABI_VERSION = 1          # SGMCMC_THIN_ABI_VERSION of include/sgmcmc_hip_thin.h (Stein thinning, K17)
 RANK_ABI_VERSION = 1          # SGMCMC_RANK_ABI_VERSION of include/sgmcmc_hip_rank.h (rank normalisation, K18)
+PSIS_ABI_VERSION = 1          # SGMCMC_PSIS_ABI_VERSION of include/sgmcmc_hip_psis.h (PSIS-LOO, K19)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
 CHAINS_MAX_CHAINS = 4096
 RANK_MAX_CHAINS = 2048        # SGMCMC_RANK_MAX_CHAINS: the 2 m split chains must fit K12
 RANK_MAX_POOLED = 8192        # SGMCMC_RANK_MAX_POOLED: pooled draws of one parameter, N = 2 m (n // 2)
+PSIS_MAX_DRAWS = 8192         # SGMCMC_PSIS_MAX_DRAWS: draws of one observation column
 SCORE_MAX_CHAINS = 64
 PREDICT_GRAD_MAX_CHAINS = 64
 
@@ -320,6 +322,11 @@ def _declare(lib):
         f = getattr(lib, "sgmcmc_rank_normalize_" + sfx)
         f.argtypes = [_vp, _ci, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _vp]
         f.restype = _ci
+    # include/sgmcmc_hip_psis.h: loglik, ld, S, n_rows, r_eff, elpd_loo, khat, n_tail, row_lppd, log_weights, ld_w, summary, stream
+    lib.sgmcmc_psis_abi_version.restype = _ci
+    lib.sgmcmc_psis_max_draws.restype = _ci
+    lib.sgmcmc_psis_loo.argtypes = [_vp, _sz, _sz, _sz, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]
+    lib.sgmcmc_psis_loo.restype = _ci
 
 
 def lib():
@@ -362,6 +369,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: Stein thinning add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_rank_abi_version() != RANK_ABI_VERSION or handle.sgmcmc_rank_max_pooled() != RANK_MAX_POOLED:
         raise SgmcmcLibraryError("pysgmcmc_amd: rank normalisation add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_psis_abi_version() != PSIS_ABI_VERSION or handle.sgmcmc_psis_max_draws() != PSIS_MAX_DRAWS:
+        raise SgmcmcLibraryError("pysgmcmc_amd: PSIS-LOO add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

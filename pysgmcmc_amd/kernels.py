@@ -13,7 +13,7 @@ import ctypes
 
 import torch
 
-from pysgmcmc_amd._lib import RANK_MAX_CHAINS, RANK_MAX_POOLED, SgmcmcLibraryError, check, lib
+from pysgmcmc_amd._lib import PSIS_MAX_DRAWS, RANK_MAX_CHAINS, RANK_MAX_POOLED, SgmcmcLibraryError, check, lib
 
 __all__ = [
     "sghmc_step", "sgld_step", "rsghmc_step", "update_step", "philox_normal", "philox_bits",
@@ -26,6 +26,7 @@ __all__ = [
     "ksd_max_samples", "ksd_workspace", "ksd_plan", "ksd",
     "stein_thin_max_samples", "stein_thin_plan", "stein_thin",
     "rank_normalize", "rank_max_pooled",
+    "psis_loo", "psis_max_draws",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -1503,3 +1504,82 @@ def rank_normalize(trace, z=None, z_folded=None, tail_lo=None, tail_hi=None):
                ld_out, chain_stride_out, _stream(trace))
     check(rc, "sgmcmc_rank_normalize")
     return z, z_folded, tail_lo, tail_hi
+
+
+def psis_max_draws():
+    """The largest number of draws ``S`` of one ``psis_loo`` call (``SGMCMC_PSIS_MAX_DRAWS``)."""
+    return PSIS_MAX_DRAWS
+
+
+def psis_loo(loglik, r_eff=1.0, elpd_loo=None, khat=None, n_tail=None, row_lppd=None, log_weights=None, summary=None):
+    """K19 (``include/sgmcmc_hip_psis.h``): Pareto-smoothed importance-sampling leave-one-out of every observation column
+    of the pointwise log densities ``loglik``, in one launch on the current stream (and a second small one for ``summary``).
+
+    ``loglik``: a float64 ``(S, n_rows)`` device tensor with dense rows (``ld = stride(0)``, a view of a wider buffer is
+    fine), ``2 <= S <= psis_max_draws()``: what ``bnn_score`` leaves in its ``loglik``. ``r_eff``: the relative efficiency of
+    the draws, a positive finite number. ``elpd_loo``, ``khat`` (float64) and ``n_tail`` (int32) ``(n_rows,)`` are allocated
+    when they are missing; optional: ``row_lppd`` float64 ``(n_rows,)``, ``log_weights`` float64 ``(S, n_rows)`` with dense
+    rows (the normalised smoothed log weights), ``summary`` float64 ``(4,)`` = ``{sum elpd_loo, sum row_lppd, rows with khat
+    > 0.7, rows holding a NaN or an infinity}``. Sizes, ``r_eff``, shapes and dtypes are checked before a device is touched,
+    in the order of the header's refusals. Returns ``(elpd_loo, khat, n_tail)``."""
+    what = "psis_loo"
+    if not torch.is_tensor(loglik):
+        raise TypeError("%s: loglik must be an (S, n_rows) float64 device tensor" % what)
+    if loglik.dim() != 2:
+        raise ValueError("%s: loglik must be (S, n_rows), got %s" % (what, tuple(loglik.shape)))
+    S, n_rows = (int(v) for v in loglik.shape)
+    if S < 2 or S > PSIS_MAX_DRAWS:
+        raise ValueError("%s: S = %d draws, must be 2 .. %d" % (what, S, PSIS_MAX_DRAWS))
+    r_eff = float(r_eff)
+    if not (r_eff > 0.0 and r_eff != float("inf")):
+        raise ValueError("%s: r_eff = %g, must be a positive finite number" % (what, r_eff))
+    if loglik.dtype != torch.float64:
+        raise TypeError("%s: loglik must be a float64 tensor, got %s" % (what, loglik.dtype))
+    if n_rows > 1 and loglik.stride(1) != 1:
+        raise ValueError("%s: the rows of loglik must be dense (stride 1 along the observations)" % what)
+    ld = int(loglik.stride(0))
+    if ld < n_rows:
+        raise ValueError("%s: ld = %d is smaller than n_rows = %d" % (what, ld, n_rows))
+    dev = loglik.device
+    for out, dt, name in ((elpd_loo, torch.float64, "elpd_loo"), (khat, torch.float64, "khat"), (n_tail, torch.int32, "n_tail"),
+                          (row_lppd, torch.float64, "row_lppd")):
+        if out is None:
+            continue
+        if not torch.is_tensor(out) or out.dtype != dt:
+            raise TypeError("%s: %s must be a %s tensor" % (what, name, dt))
+        if tuple(out.shape) != (n_rows,) or out.device != dev or not out.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous (n_rows,) = (%d,) tensor on %s" % (what, name, n_rows, dev))
+    ld_w = 0
+    if log_weights is not None:
+        if not torch.is_tensor(log_weights) or log_weights.dtype != torch.float64:
+            raise TypeError("%s: log_weights must be a %s tensor" % (what, torch.float64))
+        if tuple(log_weights.shape) != (S, n_rows) or log_weights.device != dev:
+            raise ValueError("%s: log_weights must be of shape (S, n_rows) = %s on %s, got %s" % (
+                what, (S, n_rows), dev, tuple(log_weights.shape)))
+        if n_rows > 1 and log_weights.stride(1) != 1:
+            raise ValueError("%s: the rows of log_weights must be dense" % what)
+        ld_w = int(log_weights.stride(0))
+        if ld_w < n_rows:
+            raise ValueError("%s: ld_w = %d is smaller than n_rows = %d" % (what, ld_w, n_rows))
+    if summary is not None:
+        if not torch.is_tensor(summary) or summary.dtype != torch.float64:
+            raise TypeError("%s: summary must be a %s tensor" % (what, torch.float64))
+        if summary.numel() != 4 or summary.device != dev or not summary.is_contiguous():
+            raise ValueError("%s: summary must hold 4 contiguous elements on %s" % (what, dev))
+    if n_rows >= 2 ** 31:
+        raise ValueError("%s: n_rows = %d is too large for one launch" % (what, n_rows))
+    if not loglik.is_cuda:
+        raise SgmcmcLibraryError("pysgmcmc_amd: loglik lives on %s; PSIS-LOO runs only as a HIP kernel on an AMD GPU (no CPU "
+                                 "fallback; diagnostics.psis.psis_loo_host is the host statement)." % dev)
+    if elpd_loo is None:
+        elpd_loo = torch.empty(n_rows, dtype=torch.float64, device=dev)
+    if khat is None:
+        khat = torch.empty(n_rows, dtype=torch.float64, device=dev)
+    if n_tail is None:
+        n_tail = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    opt = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib().sgmcmc_psis_loo(loglik.data_ptr(), ld, S, n_rows, r_eff, elpd_loo.data_ptr(), khat.data_ptr(),
+                                   n_tail.data_ptr(), opt(row_lppd), opt(log_weights), ld_w, opt(summary), _stream(loglik))
+    check(rc, "sgmcmc_psis_loo")
+    return elpd_loo, khat, n_tail

@@ -1141,6 +1141,45 @@ class BayesianNeuralNetwork(object):
         return dict(lppd=lppd_sum / n_rows, p_waic=p_waic, elpd_waic=lppd_sum - p_waic, rmse=rmse * y_std,
                     row_lppd=row_lppd - shift, row_pwaic=row_pwaic)
 
+    def loo(self, X=None, y=None):
+        """Pareto-smoothed importance-sampling leave-one-out of the kept networks on the observations ``X (N, D)``, ``y
+        (N,)``; the training set by default (extension, next to :meth:`score`). The device route only, for the nets
+        ``score(on_device=True)`` accepts: the kept-network matrix goes through K13 and K19 (``models.loo_score``); a net
+        the kernels refuse raises the library's error (no fallback).
+
+        Returns a dict of host values in the caller's units: ``elpd_loo`` (the sum of ``row_elpd``), ``p_loo = lppd -
+        elpd_loo`` with ``lppd`` the sum of ``row_lppd``, ``se``, ``n_bad`` (the number of observations with ``khat >
+        0.7``, whose estimate is not to be trusted), ``thinning``, and the ``(N,)`` arrays ``row_elpd``, ``row_lppd``,
+        ``khat`` and ``n_tail``. As in :meth:`score`, a density of ``y`` is the normalised one divided by ``y_std``, so the
+        rows are shifted by ``-log(y_std)``; ``p_loo``, ``se`` and ``khat`` are unchanged."""
+        from pysgmcmc_amd.models.scoring import loo_score
+        if not self.is_trained:
+            raise ValueError("Calling `bnn.loo()` on an untrained Bayesian Neural Network 'bnn' is not supported! "
+                             "Please call `bnn.train()` before calling `bnn.loo()`")
+        if (X is None) != (y is None):
+            raise ValueError("bnn.loo: X and y go together (both None: the training set)")
+        flat, sizes = self._kept_networks_matrix()
+        if X is None:
+            xd, yd = self._X_full.to(flat.device), self._Y_full.reshape(-1).to(flat.device)
+        else:
+            assert X.ndim == 2
+            yv = np.asarray(y, dtype=np.float64).reshape(-1)
+            if yv.shape[0] != X.shape[0]:
+                raise ValueError("bnn.loo: X has %d rows, y %d" % (X.shape[0], yv.shape[0]))
+            x = zero_mean_unit_var_normalization(X, self.x_mean, self.x_std)[0] if self.normalize_input else X
+            if self.normalize_output:
+                yv = zero_mean_unit_var_normalization(yv, self.y_mean, self.y_std)[0]
+            xd = torch.as_tensor(np.ascontiguousarray(x), dtype=self._torch_dtype, device=flat.device)
+            yd = torch.as_tensor(np.ascontiguousarray(yv), dtype=self._torch_dtype).to(flat.device)
+        got = loo_score(flat, xd.contiguous(), yd.contiguous(), sizes)
+        shift = float(np.log(float(self.y_std))) if self.normalize_output else 0.0
+        row_elpd, row_lppd = got.row_elpd.cpu().numpy() - shift, got.row_lppd.cpu().numpy() - shift
+        n_rows = row_elpd.shape[0]
+        return dict(elpd_loo=float(got.elpd_loo) - n_rows * shift, p_loo=float(got.p_loo), se=float(got.se),
+                    lppd=float(got.lppd) - n_rows * shift, row_elpd=row_elpd, row_lppd=row_lppd,
+                    khat=got.khat.cpu().numpy(), n_tail=got.n_tail.cpu().numpy(), n_bad=int(got.n_bad),
+                    thinning=got.thinning)
+
     def _network_input_gradients(self, x):
         """``(means, grads)``, numpy ``(n_nets, N)`` and ``(n_nets, N, D)``: the output of EVERY kept network at the rows of
         ``x`` and its gradient with respect to them, by autograd through one batched forward pass (the kept weights stacked

@@ -13,7 +13,7 @@ import torch
 from pysgmcmc_amd import kernels
 from pysgmcmc_amd.models.predictive import _trace_arguments
 
-__all__ = ["HeldOutScore", "heldout_score"]
+__all__ = ["HeldOutScore", "heldout_score", "loo_score"]
 
 HeldOutScore = collections.namedtuple("HeldOutScore", ["lppd", "p_waic", "elpd_waic", "rmse", "row_lppd", "row_pwaic",
                                                        "ens_mean", "ens_var", "sample_loglik", "loglik"])
@@ -53,3 +53,38 @@ def heldout_score(traces, X, y, layer_sizes, pointwise=False, per_sample=False):
     return HeldOutScore(lppd=summary[0] / N, p_waic=summary[1], elpd_waic=summary[0] - summary[1],
                         rmse=torch.sqrt(summary[2] / N), row_lppd=row_lppd, row_pwaic=row_pwaic, ens_mean=ens_mean,
                         ens_var=ens_var, sample_loglik=sample_loglik, loglik=loglik)
+
+
+def _strided_draws(traces, limit):
+    """``(traces, k)``: ``traces`` as they are when they hold at most ``limit`` samples in all, else every ``k``-th sample of
+    every chain, ``k`` the smallest that fits, as one matrix of rows (``FusedBNNChains.stein_discrepancy`` strides alike)."""
+    from pysgmcmc_amd.diagnostics.device_trace import _chain_matrices
+    if torch.is_tensor(traces) and traces.dim() == 3:
+        mats = list(traces.unbind(0))
+    else:
+        mats = _chain_matrices(traces)
+    m, n = len(mats), int(mats[0].shape[0])
+    if m * n <= limit:
+        return traces, 1
+    if m > limit:
+        raise ValueError("loo_score: %d chains, the limit is %d draws in all" % (m, limit))
+    k = 1
+    while m * len(range(0, n, k)) > limit:
+        k += 1
+    return torch.cat([x[::k] for x in mats], dim=0), k
+
+
+def loo_score(traces, X, y, layer_sizes, r_eff=1.0, weights=False):
+    """Pareto-smoothed importance-sampling leave-one-out of the networks sampled in ``traces`` on the observations
+    ``(X, y)`` they were trained on: K13 (:func:`heldout_score` with ``pointwise=True``) leaves the pointwise log densities
+    on the device and K19 (``diagnostics.psis_loo``) turns every observation's column into ``elpd_loo``, ``p_loo`` and the
+    Pareto shape ``khat`` that says whether the estimate can be trusted (``khat > 0.7``: it cannot).
+
+    ``traces``, ``X``, ``y``, ``layer_sizes``: what :func:`heldout_score` takes, particle matrices included. ``r_eff``: the
+    relative efficiency of the draws (1 for independent ones). More than ``kernels.psis_max_draws()`` draws in all are strided
+    evenly (every ``k``-th sample of every chain, ``k`` the smallest that fits); the result's ``thinning`` is that ``k``.
+    Returns a ``diagnostics.PsisLoo`` of device tensors; nothing waits for the host."""
+    from pysgmcmc_amd.diagnostics.psis import psis_loo
+    traces, k = _strided_draws(traces, kernels.psis_max_draws())
+    score = heldout_score(traces, X, y, layer_sizes, pointwise=True)
+    return psis_loo(score.loglik, r_eff=r_eff, weights=weights)._replace(thinning=k)

@@ -157,6 +157,18 @@ class FusedBNNChains(object):
             y = torch.as_tensor(np.asarray(y), dtype=self.storage.dtype, device=self.storage.device)
         return heldout_score(trace, X, y, self.samplers[0]._bnn_layer_sizes(), **kw)
 
+    def loo(self, X, y, trace, **kw):
+        """PSIS-LOO of the samples in ``trace`` (what :meth:`collect` returns, or anything ``models.loo_score`` accepts) on
+        the observations ``(X, y)``, with the group's own layer sizes: ``models.loo_score(trace, X, y, sizes, **kw)``, K13's
+        pointwise log densities through K19. ``X``, ``y``: as for :meth:`score`. Returns a ``diagnostics.PsisLoo`` of device
+        tensors (``elpd_loo``, ``p_loo``, ``se``, the per-observation ``khat``, ...); nothing waits for the host."""
+        from pysgmcmc_amd.models.scoring import loo_score
+        if not torch.is_tensor(X):
+            X = torch.as_tensor(np.asarray(X), dtype=self.storage.dtype, device=self.storage.device)
+        if not torch.is_tensor(y):
+            y = torch.as_tensor(np.asarray(y), dtype=self.storage.dtype, device=self.storage.device)
+        return loo_score(trace, X, y, self.samplers[0]._bnn_layer_sizes(), **kw)
+
     def predictive_gradients(self, X, trace, **kw):
         """Predictive moments of the samples in ``trace`` (what :meth:`collect` returns, or anything
         ``models.predictive_gradients`` accepts) at the rows of ``X`` and their gradients with respect to those rows, with
