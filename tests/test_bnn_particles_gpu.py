@@ -21,8 +21,9 @@ pytestmark = pytest.mark.gpu
 DEFAULT = [1, 50, 50, 50, 1]
 F32, F64 = torch.float32, torch.float64
 N_DATA = 160
-# (net, batch, dtypes): the default net; every scalar path; mixed parity; no hidden layer; B * D0 above the workgroup; the
-# LDS opt-in (f32 only: the default net in f64 fits up to batch 49)
+# (net, batch, dtypes): the default net (45 584 B of LDS in f32; 91 008 B in f64, which is already above the 64 KiB opt-in);
+# every scalar path; mixed parity; no hidden layer; B * D0 above the workgroup; the f32 ceiling of the default net (162 704 B;
+# in f64 it fits up to batch 49). The loop forms, LDS edges and grids beyond these: tests/test_bnn_particles_forms_gpu.py
 CASES = [(DEFAULT, 20, (F32, F64)), ([3, 5, 7, 1], 3, (F32, F64)), ([2, 4, 3, 1], 5, (F32, F64)), ([4, 1], 1, (F32, F64)),
          ([4, 1], 2, (F32, F64)), ([30, 6, 1], 20, (F32, F64)), (DEFAULT, 116, (F32,))]
 CASE_PARAMS = [pytest.param(sizes, B, dt, id="%s-B%d-%s" % ("x".join(map(str, sizes)), B, str(dt)[-2:]))
