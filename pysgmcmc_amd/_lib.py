@@ -58,6 +58,7 @@ KSD_ABI_VERSION = 1           # SGMCMC_KSD_ABI_VERSION of include/sgmcmc_hip_ksd
 THIN_ABI_VERSION = 1          # SGMCMC_THIN_ABI_VERSION of include/sgmcmc_hip_thin.h (Stein thinning, K17)
 RANK_ABI_VERSION = 1          # SGMCMC_RANK_ABI_VERSION of include/sgmcmc_hip_rank.h (rank normalisation, K18)
 PSIS_ABI_VERSION = 1          # SGMCMC_PSIS_ABI_VERSION of include/sgmcmc_hip_psis.h (PSIS-LOO, K19)
+CALIB_ABI_VERSION = 1         # SGMCMC_CALIB_ABI_VERSION of include/sgmcmc_hip_calib.h (PIT, coverage and CRPS, K20)
 ESS_STAGING_AUTO, ESS_STAGING_LDS, ESS_STAGING_GLOBAL = 0, 1, 2
 ESS_MAX_CHAINS = 64
 PREDICT_MAX_CHAINS = 64
@@ -65,6 +66,9 @@ CHAINS_MAX_CHAINS = 4096
 RANK_MAX_CHAINS = 2048        # SGMCMC_RANK_MAX_CHAINS: the 2 m split chains must fit K12
 RANK_MAX_POOLED = 8192        # SGMCMC_RANK_MAX_POOLED: pooled draws of one parameter, N = 2 m (n // 2)
 PSIS_MAX_DRAWS = 8192         # SGMCMC_PSIS_MAX_DRAWS: draws of one observation column
+CALIB_MAX_DRAWS = 4096        # SGMCMC_CALIB_MAX_DRAWS: draws of one predictive mixture
+CALIB_MAX_LEVELS = 16         # SGMCMC_CALIB_MAX_LEVELS
+CALIB_MAX_BINS = 64           # SGMCMC_CALIB_MAX_BINS
 SCORE_MAX_CHAINS = 64
 PREDICT_GRAD_MAX_CHAINS = 64
 
@@ -327,6 +331,13 @@ def _declare(lib):
     lib.sgmcmc_psis_max_draws.restype = _ci
     lib.sgmcmc_psis_loo.argtypes = [_vp, _sz, _sz, _sz, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]
     lib.sgmcmc_psis_loo.restype = _ci
+    # include/sgmcmc_hip_calib.h: means, ld, S, n_rows, var, y, levels, n_levels, n_bins, pit, crps, summary, stream
+    lib.sgmcmc_calib_abi_version.restype = _ci
+    lib.sgmcmc_calib_max_draws.restype = _ci
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, "sgmcmc_mixture_calibration_" + sfx)
+        f.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp, ctypes.POINTER(ctypes.c_double), _ci, _ci, _vp, _vp, _vp, _vp]
+        f.restype = _ci
 
 
 def lib():
@@ -371,6 +382,8 @@ def lib():
         raise SgmcmcLibraryError("pysgmcmc_amd: rank normalisation add-on ABI version mismatch in %s" % _LIB_PATH)
     if handle.sgmcmc_psis_abi_version() != PSIS_ABI_VERSION or handle.sgmcmc_psis_max_draws() != PSIS_MAX_DRAWS:
         raise SgmcmcLibraryError("pysgmcmc_amd: PSIS-LOO add-on ABI version mismatch in %s" % _LIB_PATH)
+    if handle.sgmcmc_calib_abi_version() != CALIB_ABI_VERSION or handle.sgmcmc_calib_max_draws() != CALIB_MAX_DRAWS:
+        raise SgmcmcLibraryError("pysgmcmc_amd: calibration add-on ABI version mismatch in %s" % _LIB_PATH)
     _lib = handle
     return handle
 

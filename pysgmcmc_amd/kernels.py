@@ -13,7 +13,7 @@ import ctypes
 
 import torch
 
-from pysgmcmc_amd._lib import PSIS_MAX_DRAWS, RANK_MAX_CHAINS, RANK_MAX_POOLED, SgmcmcLibraryError, check, lib
+from pysgmcmc_amd._lib import CALIB_MAX_BINS, CALIB_MAX_DRAWS, CALIB_MAX_LEVELS, PSIS_MAX_DRAWS, RANK_MAX_CHAINS, RANK_MAX_POOLED, SgmcmcLibraryError, check, lib
 
 __all__ = [
     "sghmc_step", "sgld_step", "rsghmc_step", "update_step", "philox_normal", "philox_bits",
@@ -27,6 +27,7 @@ __all__ = [
     "stein_thin_max_samples", "stein_thin_plan", "stein_thin",
     "rank_normalize", "rank_max_pooled",
     "psis_loo", "psis_max_draws",
+    "mixture_calibration", "calib_max_draws",
 ]
 
 _SFX = {torch.float32: "f32", torch.float64: "f64"}
@@ -1583,3 +1584,85 @@ def psis_loo(loglik, r_eff=1.0, elpd_loo=None, khat=None, n_tail=None, row_lppd=
                                    n_tail.data_ptr(), opt(row_lppd), opt(log_weights), ld_w, opt(summary), _stream(loglik))
     check(rc, "sgmcmc_psis_loo")
     return elpd_loo, khat, n_tail
+
+
+def calib_max_draws():
+    """The largest number of draws ``S`` of one ``mixture_calibration`` call (``SGMCMC_CALIB_MAX_DRAWS``)."""
+    return CALIB_MAX_DRAWS
+
+
+def mixture_calibration(means, var, y, levels=(), n_bins=0, pit=None, crps=None, summary=None):
+    """K20 (``include/sgmcmc_hip_calib.h``): the probability integral transform and the closed-form CRPS of every target
+    ``y[r]`` under the equal-weight mixture of the ``S`` Gaussians ``N(means[s][r], var[s])``, in one launch on the current
+    stream (and a second small one for ``summary``).
+
+    ``means``: a float32 or float64 ``(S, n_rows)`` device tensor with dense rows (``ld = stride(0)``, a view of a wider
+    buffer is fine), ``1 <= S <= calib_max_draws()``: what ``bnn_predict`` and ``bnn_score`` leave in their ``means``. ``var``:
+    float64 ``(S,)``, the variance of every draw's Gaussian. ``y``: ``(n_rows,)`` of ``means``' dtype. ``levels``: up to 16
+    host numbers in (0, 1), the central intervals whose coverage is counted; ``n_bins``: 0 .. 64 bins of the PIT histogram.
+    ``pit`` and ``crps`` float64 ``(n_rows,)`` are allocated when they are missing; optional: ``summary`` float64 ``(2 +
+    len(levels) + n_bins,)`` = ``{the fixed-order sum of crps, rows holding a NaN, the rows in each interval, the rows in each
+    bin}``. Sizes, levels, shapes and dtypes are checked before a device is touched, in the order of the header's refusals.
+    Returns ``(pit, crps)``."""
+    what = "mixture_calibration"
+    if not torch.is_tensor(means):
+        raise TypeError("%s: means must be an (S, n_rows) float32 or float64 device tensor" % what)
+    if means.dim() != 2:
+        raise ValueError("%s: means must be (S, n_rows), got %s" % (what, tuple(means.shape)))
+    S, n_rows = (int(v) for v in means.shape)
+    if S < 1 or S > CALIB_MAX_DRAWS:
+        raise ValueError("%s: S = %d draws, must be 1 .. %d" % (what, S, CALIB_MAX_DRAWS))
+    levels = [float(v) for v in levels]
+    n_levels, n_bins = len(levels), int(n_bins)
+    if n_levels > CALIB_MAX_LEVELS:
+        raise ValueError("%s: n_levels = %d, must be 0 .. %d" % (what, n_levels, CALIB_MAX_LEVELS))
+    if n_bins < 0 or n_bins > CALIB_MAX_BINS:
+        raise ValueError("%s: n_bins = %d, must be 0 .. %d" % (what, n_bins, CALIB_MAX_BINS))
+    for k, v in enumerate(levels):
+        if not (0.0 < v < 1.0):
+            raise ValueError("%s: levels[%d] = %g, must lie in (0, 1)" % (what, k, v))
+    if means.dtype not in _SFX:
+        raise TypeError("%s: means must be a float32 or float64 tensor, got %s" % (what, means.dtype))
+    dev = means.device
+    if not torch.is_tensor(var) or var.dtype != torch.float64:
+        raise TypeError("%s: var must be a %s tensor" % (what, torch.float64))
+    if tuple(var.shape) != (S,) or var.device != dev or not var.is_contiguous():
+        raise ValueError("%s: var must be a contiguous (S,) = (%d,) tensor on %s" % (what, S, dev))
+    if not torch.is_tensor(y) or y.dtype != means.dtype:
+        raise TypeError("%s: y must be a %s tensor, like means" % (what, means.dtype))
+    if tuple(y.shape) != (n_rows,) or y.device != dev or not y.is_contiguous():
+        raise ValueError("%s: y must be a contiguous (n_rows,) = (%d,) tensor on %s" % (what, n_rows, dev))
+    for out, name in ((pit, "pit"), (crps, "crps")):
+        if out is None:
+            continue
+        if not torch.is_tensor(out) or out.dtype != torch.float64:
+            raise TypeError("%s: %s must be a %s tensor" % (what, name, torch.float64))
+        if tuple(out.shape) != (n_rows,) or out.device != dev or not out.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous (n_rows,) = (%d,) tensor on %s" % (what, name, n_rows, dev))
+    if summary is not None:
+        if not torch.is_tensor(summary) or summary.dtype != torch.float64:
+            raise TypeError("%s: summary must be a %s tensor" % (what, torch.float64))
+        if summary.numel() != 2 + n_levels + n_bins or summary.device != dev or not summary.is_contiguous():
+            raise ValueError("%s: summary must hold 2 + n_levels + n_bins = %d contiguous elements on %s" % (
+                what, 2 + n_levels + n_bins, dev))
+    if n_rows > 1 and means.stride(1) != 1:
+        raise ValueError("%s: the rows of means must be dense (stride 1 along the observations)" % what)
+    ld = int(means.stride(0)) if S > 1 else max(int(means.stride(0)), n_rows)
+    if ld < n_rows:
+        raise ValueError("%s: ld = %d is smaller than n_rows = %d" % (what, ld, n_rows))
+    if n_rows >= 2 ** 31:
+        raise ValueError("%s: n_rows = %d is too large for one launch" % (what, n_rows))
+    if not means.is_cuda:
+        raise SgmcmcLibraryError("pysgmcmc_amd: means lives on %s; the calibration kernel runs only as a HIP kernel on an AMD "
+                                 "GPU (no CPU fallback; diagnostics.mixture_calibration_host is the host statement)." % dev)
+    if pit is None:
+        pit = torch.empty(n_rows, dtype=torch.float64, device=dev)
+    if crps is None:
+        crps = torch.empty(n_rows, dtype=torch.float64, device=dev)
+    lv = (ctypes.c_double * max(n_levels, 1))(*levels)
+    with torch.cuda.device(dev):
+        f = getattr(lib(), "sgmcmc_mixture_calibration_" + _SFX[means.dtype])
+        rc = f(means.data_ptr(), ld, S, n_rows, var.data_ptr(), y.data_ptr(), lv, n_levels, n_bins, pit.data_ptr(),
+               crps.data_ptr(), None if summary is None else summary.data_ptr(), _stream(means))
+    check(rc, "sgmcmc_mixture_calibration")
+    return pit, crps

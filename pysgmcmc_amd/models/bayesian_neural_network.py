@@ -1141,6 +1141,50 @@ class BayesianNeuralNetwork(object):
         return dict(lppd=lppd_sum / n_rows, p_waic=p_waic, elpd_waic=lppd_sum - p_waic, rmse=rmse * y_std,
                     row_lppd=row_lppd - shift, row_pwaic=row_pwaic)
 
+    def calibration(self, X_test, y_test, on_device=False, levels=(0.5, 0.8, 0.9, 0.95), n_bins=10):
+        """Calibration of the kept networks' predictive at ``X_test (N, D)`` against ``y_test (N,)`` (extension, next to
+        :meth:`score`): whether the ensemble's error bars can be believed. The predictive of a row is the equal-weight
+        mixture of the kept networks' Gaussians. Returns a dict of host values: ``pit`` ``(N,)``, the probability integral
+        transform of every target (uniform when the predictive is calibrated); ``crps`` ``(N,)`` and ``mean_crps``, the
+        continuous ranked probability score in its exact closed form; ``levels``, ``coverage`` (the share of the rows whose
+        target lies in the central interval of each level) and ``calibration_error`` (the mean of ``|coverage - levels|``);
+        ``pit_hist`` ``(n_bins,)``; ``n_bad``, the number of rows that hold a NaN; ``thinning``.
+
+        Inputs and targets are normalised and rounded as in :meth:`score`; the results are in the caller's units: ``crps``
+        and ``mean_crps`` are multiplied by ``y_std``, PIT, coverage and histogram are unchanged.
+
+        Default: ``_network_outputs`` and ``diagnostics.mixture_calibration_host`` (numpy float64 on the host).
+        ``on_device=True``: the kept-network matrix goes through K11 and K20 (``models.calibration_score``); a net the
+        kernels refuse raises the library's error (no fallback)."""
+        from pysgmcmc_amd.diagnostics.calibration import calibration_of_summary, mixture_calibration_host
+        assert X_test.ndim == 2
+        if not self.is_trained:
+            raise ValueError("Calling `bnn.calibration()` on an untrained Bayesian Neural Network 'bnn' is not supported! "
+                             "Please call `bnn.train()` before calling `bnn.calibration()`")
+        y = np.asarray(y_test, dtype=np.float64).reshape(-1)
+        if y.shape[0] != X_test.shape[0]:
+            raise ValueError("bnn.calibration: X_test has %d rows, y_test %d" % (X_test.shape[0], y.shape[0]))
+        levels = tuple(float(v) for v in levels)
+        x = zero_mean_unit_var_normalization(X_test, self.x_mean, self.x_std)[0] if self.normalize_input else X_test
+        y_std = float(self.y_std) if self.normalize_output else 1.0
+        if self.normalize_output:
+            y = zero_mean_unit_var_normalization(y, self.y_mean, self.y_std)[0]
+        y = torch.as_tensor(np.ascontiguousarray(y), dtype=self._torch_dtype)           # train's rounding of the targets
+        if on_device:
+            from pysgmcmc_amd.models.scoring import calibration_score
+            flat, sizes = self._kept_networks_matrix()
+            xd = torch.as_tensor(np.ascontiguousarray(x), dtype=self._torch_dtype, device=flat.device)
+            got = calibration_score(flat, xd, y.to(flat.device), sizes, levels=levels, n_bins=n_bins)
+            got = got._replace(**{name: getattr(got, name).cpu().numpy() for name in got._fields if name != "thinning"})
+        else:
+            outputs = self._network_outputs(x)                               # (nets, N, 2)
+            var = np.exp(outputs[:, 0, 1].astype(np.float64)) + 1e-16
+            host = mixture_calibration_host(outputs[:, :, 0], var, y.double().numpy(), levels, n_bins)
+            got = calibration_of_summary(host["pit"], host["crps"], host["summary"], levels)
+        return dict(pit=got.pit, crps=got.crps * y_std, mean_crps=float(got.mean_crps) * y_std, levels=got.levels,
+                    coverage=got.coverage, calibration_error=float(got.calibration_error), pit_hist=got.pit_hist,
+                    n_bad=int(got.n_bad), thinning=got.thinning)
+
     def loo(self, X=None, y=None):
         """Pareto-smoothed importance-sampling leave-one-out of the kept networks on the observations ``X (N, D)``, ``y
         (N,)``; the training set by default (extension, next to :meth:`score`). The device route only, for the nets

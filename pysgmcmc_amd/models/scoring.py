@@ -13,7 +13,7 @@ import torch
 from pysgmcmc_amd import kernels
 from pysgmcmc_amd.models.predictive import _trace_arguments
 
-__all__ = ["HeldOutScore", "heldout_score", "loo_score"]
+__all__ = ["HeldOutScore", "heldout_score", "loo_score", "calibration_score"]
 
 HeldOutScore = collections.namedtuple("HeldOutScore", ["lppd", "p_waic", "elpd_waic", "rmse", "row_lppd", "row_pwaic",
                                                        "ens_mean", "ens_var", "sample_loglik", "loglik"])
@@ -88,3 +88,28 @@ def loo_score(traces, X, y, layer_sizes, r_eff=1.0, weights=False):
     traces, k = _strided_draws(traces, kernels.psis_max_draws())
     score = heldout_score(traces, X, y, layer_sizes, pointwise=True)
     return psis_loo(score.loglik, r_eff=r_eff, weights=weights)._replace(thinning=k)
+
+
+def calibration_score(traces, X, y, layer_sizes, levels=(0.5, 0.8, 0.9, 0.95), n_bins=10):
+    """Calibration of the networks sampled in ``traces`` against the held-out targets ``y`` at the rows of ``X``: K11's
+    forward pass (``kernels.bnn_predict``) leaves every network's output on the device, the variance of network ``s``'s
+    Gaussian is ``exp((double)log_var_s) + 1e-16`` from the last parameter of its sample row, and K20
+    (``diagnostics.calibration``) turns every row's mixture into the probability integral transform of its target and the
+    closed-form CRPS, and counts the coverage of the central ``levels`` and the PIT histogram of ``n_bins`` bins.
+
+    ``traces``, ``X``, ``y``, ``layer_sizes``: what :func:`heldout_score` takes, particle matrices included. More than
+    ``kernels.calib_max_draws()`` draws in all are strided evenly (every ``k``-th sample of every chain, ``k`` the smallest
+    that fits); the result's ``thinning`` is that ``k``. Returns a ``diagnostics.Calibration`` of device tensors, in the units
+    the networks work in; nothing waits for the host."""
+    from pysgmcmc_amd.diagnostics.calibration import calibration
+    traces, k = _strided_draws(traces, kernels.calib_max_draws())
+    chains, sizes, first, S, N = _trace_arguments("calibration_score", traces, X, layer_sizes, y)
+    if N == 0:
+        raise ValueError("calibration_score: X holds no rows, so there is nothing to score")
+    means = torch.empty(S, N, dtype=first.dtype, device=first.device)
+    kernels.bnn_predict(chains, sizes, X, means)
+    last = kernels._bnn_n_params(sizes) - 1
+    mats = [chains] if torch.is_tensor(chains) else chains
+    log_var = torch.cat([x[..., last].reshape(-1) for x in mats])
+    var = torch.exp(log_var.double()) + 1e-16
+    return calibration(means, var, y, levels=levels, n_bins=n_bins)._replace(thinning=k)

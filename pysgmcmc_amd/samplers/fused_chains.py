@@ -169,6 +169,19 @@ class FusedBNNChains(object):
             y = torch.as_tensor(np.asarray(y), dtype=self.storage.dtype, device=self.storage.device)
         return loo_score(trace, X, y, self.samplers[0]._bnn_layer_sizes(), **kw)
 
+    def calibration(self, X, y, trace, **kw):
+        """Calibration of the samples in ``trace`` (what :meth:`collect` returns, or anything ``models.calibration_score``
+        accepts) against the held-out targets ``y`` at the rows of ``X``, with the group's own layer sizes:
+        ``models.calibration_score(trace, X, y, sizes, **kw)``, K11's means through K20. ``X``, ``y``: as for :meth:`score`.
+        Returns a ``diagnostics.Calibration`` of device tensors (``pit``, ``crps``, ``mean_crps``, ``coverage``, ``pit_hist``,
+        ...); nothing waits for the host."""
+        from pysgmcmc_amd.models.scoring import calibration_score
+        if not torch.is_tensor(X):
+            X = torch.as_tensor(np.asarray(X), dtype=self.storage.dtype, device=self.storage.device)
+        if not torch.is_tensor(y):
+            y = torch.as_tensor(np.asarray(y), dtype=self.storage.dtype, device=self.storage.device)
+        return calibration_score(trace, X, y, self.samplers[0]._bnn_layer_sizes(), **kw)
+
     def predictive_gradients(self, X, trace, **kw):
         """Predictive moments of the samples in ``trace`` (what :meth:`collect` returns, or anything
         ``models.predictive_gradients`` accepts) at the rows of ``X`` and their gradients with respect to those rows, with
